@@ -2,6 +2,7 @@
 """bench.py - tri-modal images/sec, forward+backward+optimizer step, of the EDITOR hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|f16|f16x2|f32] [--preset RGBNT201|RGBNT100|MSVR310|SYNTH4L]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,9 +15,13 @@ zero_grad -> forward -> loss (pairs + aux) -> backward (+ gradient all-reduce, o
 seconds per iteration of a loop that hands every step its batch from pinned host memory (processor.py:73-78; the copy of
 batch i+1 is pipelined under step i, as a prefetching loader does) and synchronises the device every iteration; K iterations
 between a barrier + synchronize on both sides, MAX over ranks.  `replay_only`: the bare step beside it (inputs resident,
-one synchronisation at the end; N = 1 only).
+one synchronisation at the end; N = 1 only, --full).
 
-One JSON line on rank 0.
+One JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`,
+`config`); the blocks below measure more and are computed with --full only.
+  --dump-outputs DIR  after the timed steps: what the LAST timed step handed its caller, as DIR/<name>.npy (float32; the loss
+                float64) - the loss, every forward output, and a fixed seeded sample of the updated parameters and of their
+                gradients (at most 64 MB in all).  The inputs are seeded, so two builds can be compared output for output.
   roofline      the dominant kernel family (16-bit MFMA GEMM): algorithmic FLOPs of every launch of one step / their
                 HIP-event durations (replayed back to back after the timed region), against the 2.5 PFLOP/s dense peak;
                 `traffic` = HBM bytes per step of those launches from the committed PMC profile of the same command
@@ -31,7 +36,7 @@ One JSON line on rank 0.
                 (cls4t relative error, token-selection agreement), so the speed is never read without the parity it buys.
   other_configs BASELINE.json configs 3 / 4 / 5 (RGBNT100, MSVR310 384x128, the synthetic 4-modal ViT-L) on this one GPU: the same timed loop
                 in a child process per preset - per-GPU workloads of configs quoted on 8 GPUs, so that the driver's own run carries
-                a number for each; not part of `value`.  N = 1 default line only (--no-others skips it).
+                a number for each; not part of `value`.  N = 1 --full line only (--no-others skips it).
   cpu_baseline  the oracle (CPU restatement pinned to the reference) timed on this host's cores: the same step at B=128
                 (1 warm-up + 3 timed iterations: forward, the reference's loss, backward, SGD) and config 1 (`c1`: B=32,
                 RGB only, backbone forward).  N = 1 only.
@@ -466,7 +471,7 @@ def modes_block(args, cfg, cams, own_value, own_eval=None):
         else:
             steps, warm = (3, 1) if dt == "f32" else (args.steps, args.warmup)
             cmd = [sys.executable, os.path.abspath(__file__), "--dtype", dt, "--preset", args.preset, "--batch", str(args.batch),
-                   "--steps", str(steps), "--warmup", str(warm), "--graph", "--no-cpu-baseline", "--no-replay", "--no-modes"]
+                   "--steps", str(steps), "--warmup", str(warm), "--graph", "--full", "--no-cpu-baseline", "--no-replay", "--no-modes"]
             if args.no_h2d:
                 cmd.append("--no-h2d")
             try:
@@ -681,6 +686,61 @@ def cpu_baseline(model, cfg, cams, batch, iters):
     return res
 
 
+DUMP_SAMPLE = 1 << 20              # elements per dumped array at most (a larger one is sampled at fixed seeded positions)
+DUMP_BUDGET = 64 << 20             # bytes of one --dump-outputs directory at most
+
+
+def _sample(x, seed):
+    """x flattened; all of it when it is small enough, else DUMP_SAMPLE elements at seeded positions (the same ones in every run
+    with the same shapes)."""
+    flat = x.reshape(-1)
+    if flat.numel() <= DUMP_SAMPLE:
+        return flat
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(path, loss, outs, model):
+    """--dump-outputs: what the LAST timed step handed its caller - the loss (float64), every forward output (float32), and the
+    step's effect on the model: a seeded sample of the updated parameters and of the gradients they were updated with (float32,
+    the parameters in named_parameters() order, flattened).  Written as <path>/<name>.npy, DUMP_BUDGET bytes in all at most."""
+    import numpy as np
+    params = [p for _, p in model.named_parameters()]
+    arrays = {"loss": loss.detach().double().reshape(1)}
+    for i, o in enumerate(outs):
+        arrays["output_%d" % i] = _sample(o.detach().float(), 1000 + i)
+    with torch.no_grad():
+        flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+        arrays["params_sample"] = _sample(flat_p, 2000)
+        del flat_p
+        flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+        arrays["grads_sample"] = _sample(flat_g, 2000)
+        del flat_g
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than the {DUMP_BUDGET} allowed")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(arrays)
+
+
+def _argv_abs_dump(argv, path):
+    """argv with the --dump-outputs directory made absolute (the rank launcher starts its ranks in the repository root)."""
+    out, i = [], 0
+    while i < len(argv):
+        a = argv[i]
+        if a == "--dump-outputs" and i + 1 < len(argv):
+            out += [a, path]
+            i += 2
+            continue
+        out.append("--dump-outputs=" + path if a.startswith("--dump-outputs=") else a)
+        i += 1
+    return out
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
@@ -763,7 +823,7 @@ def launch_ranks(n, argv):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = argparse.ArgumentParser(allow_abbrev=False)     # (no abbreviations: the rank launcher rewrites --dump-outputs by name)
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=3)
@@ -788,13 +848,21 @@ def main():
     ap.add_argument("--no-others", action="store_true", help="skip the other BASELINE configs' child runs (`other_configs`)")
     ap.add_argument("--spawn", action="store_true", help="go through the rank launcher even for --gpus 1 (a real 1-rank RCCL group; "
                     "also EDITOR_BENCH_SPAWN=1)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: replay_only, roofline, eval, "
+                    "modes, other_configs, cpu_baseline, torch_gpu_yardstick (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "computed as DIR/<name>.npy (see the module docstring)")
     args = ap.parse_args()
+    argv = sys.argv[1:]
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+        argv = _argv_abs_dump(argv, args.dump_outputs)
     if args.batch is None:
         args.batch = 32 if args.preset == "SYNTH4L" else 128
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.spawn or os.environ.get("EDITOR_BENCH_SPAWN") == "1"):
-        sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
+        sys.exit(launch_ranks(args.gpus, argv))
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but the launcher started WORLD_SIZE={os.environ['WORLD_SIZE']} ranks")
 
@@ -809,7 +877,7 @@ def main():
     if world == 1 and not args.graph and not args.no_graph and not force_ddp:
         import subprocess
         try:
-            cp = subprocess.run([sys.executable, os.path.abspath(__file__)] + sys.argv[1:] + ["--graph"],
+            cp = subprocess.run([sys.executable, os.path.abspath(__file__)] + argv + ["--graph"],
                                 stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=2400)
             lines = [ln for ln in cp.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
             if cp.returncode == 0 and lines:
@@ -884,12 +952,17 @@ def main():
     img = {k: v.to(dev) for k, v in img_h.items()}
     label, cam, view = label.to(dev), cam.to(dev), view.to(dev)
     writer = _Writer()
+    # --dump-outputs: the forward outputs of the latest step (views, no copy; in the captured step they are the graph's own
+    # output buffers, which every replay rewrites)
+    last_out = [] if args.dump_outputs else None
 
     def step():
         opt.zero_grad(set_to_none=True)
         if buckets is not None and os.environ.get("EDITOR_BCAST_BUFFERS", "1") != "0":
             buckets.broadcast_buffers(model)       # DDP's per-forward broadcast_buffers (train_net.py:63-64: the default)
         out = model(img, label=label, cam_label=cam, view_label=view, img_path=None, writer=writer, epoch=1)
+        if last_out is not None:
+            last_out[:] = [o.detach() for o in out]
         loss = losses.loss_pairs(out, label)
         loss.backward()
         if buckets is not None:
@@ -916,7 +989,8 @@ def main():
         for _ in range(args.warmup):
             step()
     probe = _GemmProbe()
-    probe.install()
+    if args.full:
+        probe.install()
     # the whole step (forward, loss, backward incl. the bucket all-reduces, fused SGD: ~1100 launches) is captured once
     # into a hipGraph and the timed region replays it; the drop-path generator and the SGD pointer table are replay-safe
     # (device-resident counter, captured upload).
@@ -926,13 +1000,15 @@ def main():
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 step()                                            # allocator / lazy-attribute warm-up on the capture stream
-                probe.recording = rank == 0 and not args.no_replay   # the GEMM launch list of one (eager) step: it keeps that
+                probe.recording = args.full and rank == 0 and not args.no_replay   # the GEMM launch list of one (eager) step: it keeps that
                                                                   # step's operands alive for the replay (--no-replay: config 5 at B = 64)
                 step()
                 probe.recording = False
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             opt.zero_grad(set_to_none=True)
+            if last_out is not None:
+                last_out.clear()                                  # (the eager steps' outputs are not freed inside the capture)
             # the eager warm-up steps leave their activations CACHED in the allocator's ordinary pool; the capture allocates
             # the same set again from the graph's private pool - hand the cached blocks back first, or large configurations
             # (config 5 at B = 64: ~120 GB of saved activations) need twice their memory
@@ -1028,7 +1104,7 @@ def main():
                 graph.replay()
                 loss_ = static_loss
             else:
-                probe.recording = rank == 0 and i == args.steps - 1 and not probe.calls and not args.no_replay
+                probe.recording = args.full and rank == 0 and i == args.steps - 1 and not probe.calls and not args.no_replay
                 loss_ = step()
                 probe.recording = False
             if feeding:
@@ -1053,14 +1129,17 @@ def main():
 
     rank_ms = []
     elapsed, loss = timed_loop(feed)
+    dumped = None
+    if args.dump_outputs and rank == 0:                  # before anything below runs the step again
+        dumped = dump_outputs(args.dump_outputs, loss, last_out, model)
     replay_only = None
-    if feed and world == 1 and not force_ddp:            # the bare step beside it (inputs resident, no per-iteration sync)
+    if args.full and feed and world == 1 and not force_ddp:   # the bare step beside it (inputs resident, no per-iteration sync)
         el2, _ = timed_loop(False)
         replay_only = {"value": round(b * args.steps / el2, 2), "ms_per_step": round(1e3 * el2 / args.steps, 3),
                        "what": "same K steps with the inputs resident in HBM and one synchronisation at the end"}
     probe.recording = False
     situ = None
-    if rank == 0 and world == 1 and not force_ddp and not args.no_replay and args.dtype != "f32":
+    if args.full and rank == 0 and world == 1 and not force_ddp and not args.no_replay and args.dtype != "f32":
         if graph is not None:                             # (eager steps of a capturing process stay off the default stream, see above)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -1068,13 +1147,15 @@ def main():
             torch.cuda.current_stream().wait_stream(side)
         else:
             situ = probe.in_situ(step)                    # one more (untimed) eager step, every GEMM launch timed in place
-    probe.remove()
+    if args.full:
+        probe.remove()
     lossv = float(loss.detach())
     eval_block = None
-    if rank == 0 and world == 1 and not force_ddp and not args.no_eval:
+    if args.full and rank == 0 and world == 1 and not force_ddp and not args.no_eval:
         eval_block = eval_throughput(model, img, cam, view, b, max(args.steps, 3))
 
-    if rank == 0:
+    def roofline_block():
+        """--full: the dominant kernel family against its peak (module docstring, `roofline`)."""
         kinds = {} if args.no_replay else probe.replay()
         flops = sum(v[0] for v in kinds.values())
         ms = sum(v[1] for v in kinds.values())
@@ -1090,8 +1171,6 @@ def main():
             achieved = s_flops / (s_ms * 1e-3) / 1e12 if s_ms > 0 else None
         else:
             s_flops, s_ms, achieved = flops, ms, achieved_replay
-        ms_step = 1e3 * elapsed / args.steps
-        arch = cfg.MODEL.TRANSFORMER_TYPE.replace("_patch16_224", "").replace("vit_", "ViT-").replace("base", "B").replace("large", "L")
         # `traffic` / `alg_bytes_per_step` are NOT measured in this run: PMC counters need their own rocprofv3 passes
         # (MI355X_MICROARCH.md), so the figure is read from the newest committed profile of this same command
         # (tools/pmc_traffic.sh -> profiles/rNN_pmc_traffic.json) and labelled as such (`traffic_source`)
@@ -1161,6 +1240,11 @@ def main():
                                         "256 MB Infinity Cache); in_situ_*: the same kernel's average duration inside the step (source: "
                                         "hbm_kernels_in_situ_source) - there its operands were written by the previous kernel and are partly "
                                         "cache-resident (a fraction above 1 is that, not a faster HBM)")
+        return roof
+
+    ms_step = 1e3 * elapsed / args.steps
+    if rank == 0:
+        arch = cfg.MODEL.TRANSFORMER_TYPE.replace("_patch16_224", "").replace("vit_", "ViT-").replace("base", "B").replace("large", "L")
         out = {
             "metric": "tri-modal images/sec fwd+bwd @ B=128 ViT-B",
             "value": round(world * b * args.steps / elapsed, 2),
@@ -1178,26 +1262,29 @@ def main():
                        "launch": ("hipGraph replay" + (" incl. RCCL bucket all-reduces (overlapped with backward)" if use_dist else ""))
                        if graph is not None else ("eager" + (", RCCL bucket all-reduces overlapped with backward" if use_dist else "")),
                        "grad_buckets": None if buckets is None else buckets.describe()},
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roofline_block()
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": args.dump_outputs, "arrays": dumped}
         if use_dist:
             # what the driver needs to see that RCCL really ran N ranks: the group's size as torch.distributed reports it after
             # init, and every rank's own time for its K steps (before the closing barrier; `ms_per_step` is the max incl. it)
             out["rccl_ranks"] = dist.get_world_size()
             out["rank_ms_per_step"] = {"min": min(rank_ms), "max": max(rank_ms), "all": rank_ms}
             out["not_in_this_line"] = ("modes, cpu_baseline, replay_only and torch_gpu_yardstick are single-process blocks of the "
-                                       "N = 1 line (python bench.py --gpus 1)")
+                                       "N = 1 line (python bench.py --gpus 1 --full)")
         if eval_block is not None:
             out["eval"] = eval_block
         if replay_only is not None:
             out["replay_only"] = replay_only
-        if world == 1 and not args.no_modes and not force_ddp and args.preset in ("RGBNT201", "RGBNT100", "MSVR310"):
+        if args.full and world == 1 and not args.no_modes and not force_ddp and args.preset in ("RGBNT201", "RGBNT100", "MSVR310"):
             out["modes"] = modes_block(args, cfg, cams, out["value"], eval_block)
             out["value_at_parity"] = out["modes"].pop("value_at_parity")
-        if (world == 1 and not force_ddp and not args.no_others and not args.no_modes and args.preset == "RGBNT201" and b == 128
-                and args.dtype != "f32"):
-            out["other_configs"] = other_configs_block(args)       # (with the full default line only: the modes' children pass --no-modes)
-        if world == 1 and not args.no_cpu_baseline and not force_ddp:
+        if (args.full and world == 1 and not force_ddp and not args.no_others and not args.no_modes and args.preset == "RGBNT201"
+                and b == 128 and args.dtype != "f32"):
+            out["other_configs"] = other_configs_block(args)       # (with the --full default line only: the modes' children pass --no-modes)
+        if args.full and world == 1 and not args.no_cpu_baseline and not force_ddp:
             out["cpu_baseline"] = cpu_baseline(model, cfg, cams, b, args.cpu_iters)
             if args.preset == "RGBNT201" and b == 128:
                 out["torch_gpu_yardstick"] = torch_gpu_yardstick()

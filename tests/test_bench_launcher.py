@@ -148,3 +148,45 @@ def test_source_hash_moves_with_a_kernel_source(bench, monkeypatch, tmp_path):
     assert h0 == bench.source_hash() and len(h0) == 16
     (root / "editor_amd/csrc/a.hip").write_text("kernel 2")
     assert bench.source_hash() != h0
+
+
+def test_dump_outputs_path_reaches_the_ranks_absolute(bench, monkeypatch, tmp_path):
+    """--dump-outputs DIR: the ranks start in the repository root, so a relative DIR is handed on as the caller's absolute path."""
+    seen = {}
+    _patch(monkeypatch, bench, 8, _line(2) + "\n", 0, seen)
+    monkeypatch.chdir(tmp_path)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--steps", "3", "--dump-outputs", "d1"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 0
+    tail = seen["cmd"][seen["cmd"].index(os.path.join(ROOT, "bench.py")) + 1:]
+    assert tail == ["--gpus", "2", "--steps", "3", "--dump-outputs", str(tmp_path / "d1")]
+    assert bench._argv_abs_dump(["--dump-outputs=x", "--full"], "/a/x") == ["--dump-outputs=/a/x", "--full"]
+
+
+def test_dump_outputs_writes_the_step_outputs_and_a_fixed_sample(bench, monkeypatch, tmp_path):
+    """What --dump-outputs writes: loss (float64), every output (float32), a parameter and a gradient sample at seeded positions -
+    the same positions in every run, small arrays whole, DUMP_BUDGET bytes at most."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 64)
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(30, 20), torch.nn.Linear(20, 5))
+    x = torch.randn(7, 30)
+    y = model(x)
+    loss = y.pow(2).mean()
+    loss.backward()
+    names = bench.dump_outputs(str(tmp_path / "a"), loss, [y, x.to(torch.bfloat16)], model)
+    assert names == ["grads_sample", "loss", "output_0", "output_1", "params_sample"]
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert got["loss"].dtype == np.float64 and got["loss"][0] == loss.item()
+    assert got["output_0"].dtype == np.float32 and np.array_equal(got["output_0"], y.detach().numpy().reshape(-1))   # 35 <= 64: whole
+    assert got["output_1"].dtype == np.float32 and got["output_1"].size == 64                                    # 210 > 64: sampled
+    assert got["params_sample"].size == got["grads_sample"].size == 64
+    assert set(got["params_sample"]) <= set(torch.cat([p.detach().reshape(-1) for p in model.parameters()]).numpy())
+    bench.dump_outputs(str(tmp_path / "b"), loss, [y, x.to(torch.bfloat16)], model)
+    for n in names:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / (n + ".npy")))
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 100)
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "c"), loss, [y], model)

@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
     cp = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "16",
-                         "--no-modes", "--cpu-iters", "1"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200,
-                        cwd=ROOT)
+                         "--full", "--no-modes", "--cpu-iters", "1"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                        timeout=1200, cwd=ROOT)
     assert cp.returncode == 0, cp.stderr[-2000:]
     lines = [ln for ln in cp.stdout.splitlines() if ln.strip()]
     assert lines and lines[-1].startswith("{"), cp.stdout[-500:]
@@ -49,7 +49,7 @@ def test_bench_starts_its_own_ranks():
     same launcher is exercised here with one rank (`--spawn`): a real 1-rank RCCL group, bucket all-reduces issued from inside
     the backward, rank 0's JSON line relayed as the only line of stdout."""
     cp = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--steps", "3", "--warmup", "1",
-                         "--batch", "16"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200, cwd=ROOT)
+                         "--batch", "16", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200, cwd=ROOT)
     assert cp.returncode == 0, cp.stderr[-3000:]
     lines = [ln for ln in cp.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), cp.stdout[-800:]
@@ -64,6 +64,47 @@ def test_bench_starts_its_own_ranks():
     assert j["value"] > 0 and abs(j["value"] - 16 * 3 / (j["ms_per_step"] * 3e-3)) / j["value"] < 0.02
     assert len(j["rank_ms_per_step"]["all"]) == 1 and j["rank_ms_per_step"]["max"] <= j["ms_per_step"] * 1.001
     assert j["config"]["grad_buckets"]
+
+
+def test_plain_bench_times_the_steps_and_dumps_the_last_ones_outputs(tmp_path):
+    """The plain line (no --full): the headline fields only; --steps K really runs K timed iterations (EDITOR_BENCH_ITER_TIMES=1: one
+    wall time per timed iteration on stderr); --dump-outputs writes what the last timed step computed - the loss, the forward outputs
+    and a parameter / gradient sample - as float32 / float64 .npy files, 64 MB at most, and a second run with the same arguments
+    (same seeded inputs) writes the same values."""
+    import numpy as np
+    env = dict(os.environ, EDITOR_BENCH_ITER_TIMES="1")
+    runs = []
+    for name in ("dump_a", "dump_b"):
+        cp = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch",
+                             "16", "--dump-outputs", name], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600,
+                            cwd=str(tmp_path), env=env)       # (a relative directory: the timing child must write it there too)
+        assert cp.returncode == 0, cp.stderr[-2000:]
+        lines = [ln for ln in cp.stdout.splitlines() if ln.strip()]
+        assert lines and lines[-1].startswith("{"), cp.stdout[-500:]
+        j = json.loads(lines[-1])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in j, key
+        for key in ("roofline", "eval", "replay_only", "modes", "other_configs", "cpu_baseline", "torch_gpu_yardstick"):
+            assert key not in j, key                     # --full only
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["dtype"] == "bf16" and j["higher_is_better"] is True
+        iters = [ln for ln in cp.stderr.splitlines() if ln.startswith("iteration ms:")]
+        assert iters, cp.stderr[-2000:]
+        it_ms = [float(v) for v in iters[-1].split(":", 1)[1].split()]
+        assert len(it_ms) == 3                           # the timed region ran exactly --steps iterations
+        assert abs(sum(it_ms) / 3 - j["ms_per_step"]) <= 0.05 * j["ms_per_step"] + 0.2
+        out_dir = tmp_path / name
+        files = sorted(p.name for p in out_dir.iterdir())
+        assert files == sorted(n + ".npy" for n in j["outputs_dumped"]["arrays"])
+        assert {"loss.npy", "output_0.npy", "output_1.npy", "params_sample.npy", "grads_sample.npy"} <= set(files)
+        arrays = {f: np.load(out_dir / f) for f in files}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all() for a in arrays.values())
+        assert arrays["loss.npy"].dtype == np.float64 and arrays["params_sample.npy"].size == arrays["grads_sample.npy"].size
+        assert arrays["output_0.npy"].size == 16 * 171 and arrays["output_1.npy"].size == 16 * 2304      # score, cls4t (RGBNT201)
+        assert np.abs(arrays["grads_sample.npy"]).max() > 0
+        runs.append(arrays)
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
 
 
 def test_bench_refuses_more_ranks_than_gpus_loudly():

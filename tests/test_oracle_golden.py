@@ -147,14 +147,23 @@ def test_f8_retrieval_metrics():
     nq = 48
     feats, pids, camids, scenes = _retrieval_case(int(g["seed"]), nq, 200, 64, 12, 4)
     cmc, m_ap, dist = mr.r1_map_eval(feats, pids, camids, nq, max_rank=50)
-    assert np.array_equal(dist[:8], g["dist"])
+    # The distances are float32 |q|^2 + |g|^2 - 2 q.g; their last bit depends on the host CPU: F.normalize's row reduction under some
+    # ATen CPU capabilities (ATEN_CPU_CAPABILITY=default: 2 ulps of `dist`) and the addmm_ kernel of some CPUs (1 ulp in 10 of the
+    # 1600 pinned entries of `dist` and of `raw`, with identical features and squared norms).  So the distances are pinned to
+    # 4 ulps of their own value; the ranking exactly up to neighbours that close, the metrics exactly.
+    def ulps(x, ref):
+        return np.abs(x.astype(np.float64) - ref) / np.spacing(np.abs(ref).astype(np.float32))
+
+    assert ulps(dist[:8], g["dist"]).max() <= 4
     assert np.array_equal(cmc, g["cmc"]) and m_ap == float(g["mAP"])
-    assert np.array_equal(np.argsort(dist, axis=1)[:, :50], g["order"])
+    order = np.argsort(dist, axis=1)[:, :50]
+    moved = order != g["order"]                          # a swap only between neighbours within 4 ulps of each other
+    assert np.all(ulps(np.take_along_axis(dist, order, axis=1), np.take_along_axis(dist, g["order"], axis=1))[moved] <= 4)
     cmc_s, map_s, _ = mr.eval_func(dist, pids[:nq], pids[nq:], scenes[:nq], scenes[nq:], 50)
     assert np.array_equal(cmc_s, g["cmc_scene"]) and map_s == float(g["mAP_scene"])
     raw = mr.euclidean_distance(feats[:nq], feats[nq:])
     cmc_r, map_r, _ = mr.eval_func(raw, pids[:nq], pids[nq:], camids[:nq], camids[nq:], 20)
-    assert np.array_equal(raw[:8], g["dist_raw"])
+    assert ulps(raw[:8], g["dist_raw"]).max() <= 4
     assert np.array_equal(cmc_r, g["cmc_raw"]) and map_r == float(g["mAP_raw"])
 
 

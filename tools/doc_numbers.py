@@ -5,7 +5,8 @@ disagree ("30.4 vs 30.84").
     python tools/doc_numbers.py --check    # exit 1 if a block differs from what the files give (tests/test_host.py runs this)
 
 A block is everything between `<!-- BEGIN GENERATED: <name> -->` and `<!-- END GENERATED: <name> -->`.  Sources (profiles/):
-    r06_bench_line_default.json        the driver's command (`python bench.py`), builder-run on one MI355X
+    r06_bench_line_default.json        the full bench line (`python bench.py --full`; plain `python bench.py` when it was taken, before
+                                       --full existed), builder-run on one MI355X
     r06_bench_line_noskip.json         the same with EDITOR_DROP_SKIP=0 (stochastic-depth compaction off), same box, same call
     r06_bench_line_{f16,f16x2,f16x2s,rgbnt100,msvr310,synth4l}.json
     r06_bench_kernel_stats_serial.csv  rocprofv3 --kernel-trace --stats of the bench command, weight gradients on the main stream

@@ -6,8 +6,8 @@ hot path's two extreme shapes, timed call by call with HIP events under the step
   cold: a 512 MB fill between calls (boost clock, A comes from HBM - what a block's GEMMs see in the step)
 and for two reduction lengths, so that the K-tile cost comes out by difference (the tile ends cancel):
     us per K-tile = (t[K = 3072] - t[K = 768]) / 36
-Run it again under a capped shader clock (tools/gemm_bound_probe.sh tries `rocm-smi --setperfdeterminism`): a matrix-core-bound loop
-scales with the clock, a delivery-bound one does not.
+Compared across shader clocks, a matrix-core-bound loop scales with the clock, a delivery-bound one does not (this probe does not
+change the clock).
     python tools/gemm_bound_probe.py
 """
 import os

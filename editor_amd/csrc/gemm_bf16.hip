@@ -938,7 +938,10 @@ __device__ __forceinline__ void pp_body(const GemmB16Args& g, const int bid, con
     if (g.m_live) {
         const int live = *g.m_live;
         if (g.live_is_k) ktiles = min(ktiles, (live + BK - 1) / BK);
-        else if (!g.linear_ids) tiles_m = min(tiles_m, (live + TH - 1) / TH);
+        // (forward / dgrad: the tiles cover roundup64(live), not just live - the live-row reductions downstream (weight gradients,
+        //  whole 64-row K-tiles) read rows [live, roundup64(live)) of this output, and with 208-row tiles roundup208(live) can fall
+        //  short of them: 0 * unwritten = NaN.  Those rows come from the zero rows of the compacted operand, so they are finite)
+        else if (!g.linear_ids) tiles_m = min(tiles_m, ((live + BK - 1) / BK * BK + TH - 1) / TH);
     }
     const int nwg = tiles_m * g.tiles_n;
     if (!g.linear_ids && bid >= nwg) {
@@ -1372,6 +1375,9 @@ __device__ __forceinline__ void pp_body(const GemmB16Args& g, const int bid, con
         bf16_t* Cb = reinterpret_cast<bf16_t*>(g.C);
         bf16_t* Ab = reinterpret_cast<bf16_t*>(g.aux);
         float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // column sums of this thread's 8 columns (same for all its rows)
+        // live rows (stochastic-depth-compacted operand): the sums stop at *m_live - behind it the tile's rows are zeros (A rows
+        // [live, roundup64)) or rows nobody reads (A rows past roundup64(live) need not be written: 0 * garbage there)
+        const int cs_rows = (g.colsum && g.m_live && !g.live_is_k) ? min(g.M, *g.m_live) : g.M;
 #pragma unroll 4
         for (int it = 0; it < 16; ++it) {
             const int c = threadIdx.x + it * 512;
@@ -1418,7 +1424,7 @@ __device__ __forceinline__ void pp_body(const GemmB16Args& g, const int bid, con
                 if (Ab) *reinterpret_cast<uint4*>(Ab + (long)m * g.ldaux + n) = want_grad ? make_uint4(dw_[0], dw_[1], dw_[2], dw_[3]) : p;
                 p = make_uint4(pw[0], pw[1], pw[2], pw[3]);
             }
-            if (g.colsum) {
+            if (g.colsum && m < cs_rows) {
                 const uint32_t pw[4] = {p.x, p.y, p.z, p.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { const v2f_t u = H16<F16>::unpack2(pw[e]); cs[2 * e] += u.x; cs[2 * e + 1] += u.y; }

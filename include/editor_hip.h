@@ -275,8 +275,9 @@ int editor_gemm_f16(const uint16_t* A, const uint16_t* B, void* C, int c_f32, in
 
 /* m_live (device int32 scalar, may be NULL) - compacted HMA without a host round trip: buffers and launches are sized
  * for the worst-case row count, only the first *m_live token rows are live.  Row kernels process rows below
- * roundup64(*m_live) (rows in [*m_live, roundup64) carry mask 0 / zeros), GEMMs skip tiles of dead rows (forward, dgrad)
- * or shorten the reduction (wgrad: transA); dead rows are never read by anyone. */
+ * roundup64(*m_live) (rows in [*m_live, roundup64) carry mask 0 / zeros), GEMMs skip tiles of dead rows (forward, dgrad: the
+ * tiles still cover roundup64(*m_live), see editor_gemm_h16_rows) or shorten the reduction (wgrad: transA); dead rows are never
+ * read by anyone. */
 
 /* Attention.forward / AttentionMask.forward on packed qkv rows (B*T, 3*heads*hd) (vit_pytorch.py:184-198,240-258).
  * mask (B,T) uint8 or NULL.  out (B*T, heads*hd).  probs (B,heads,T,T) fp32: the softmax output the backbone
@@ -570,7 +571,14 @@ int editor_cast_rows_colsum_perm_parts(const float* in, const float* rowscale, l
                                        float* workspace, int ws_rows, float scale, const int* perm, int* nparts,
                                        editor_stream_t stream);
 /* editor_gemm_bf16 / _f16 (dtype 1 / 2; A (M,K), B (N,K) k-major, fp32 C, EDITOR_EPI_RESIDUAL) on compacted rows: output row m is
- * scattered to row rowmap[m] of C, reading aux and rowscale there (rowmap = inv of editor_droppath_plan); m_live as editor_gemm_bf16. */
+ * scattered to row rowmap[m] of C, reading aux and rowscale there (rowmap = inv of editor_droppath_plan); m_live as editor_gemm_bf16.
+ * Unwritten-row contract of the compacted MLP branch (m_live = the live prefix; rows [*m_live, M) of its operands are zero):
+ *  - a live-row PRODUCER (forward / dgrad GEMM with m_live) writes every row below roundup64(*m_live) - whole tiles, whatever the
+ *    tile height, the rows behind *m_live computed from the zero operand rows (finite) - and may leave the rows past its last tile
+ *    unwritten; this row-scatter form writes only the rows below *m_live;
+ *  - a live-row REDUCTION reads nothing at or past roundup64(*m_live): the weight gradients (editor_gemm_wgrad_group_live) reduce
+ *    over whole 64-row K-tiles, i.e. rows [*m_live, roundup64) must be finite with one operand zero there; the column sums of a
+ *    live-row dgrad (EDITOR_EPI_COLSUM) and the compacted LayerNorm backward (dy_live) read nothing at or past *m_live. */
 int editor_gemm_h16_rows(int dtype, const uint16_t* A, const uint16_t* B, void* C, int M, int N, int K, long lda, long ldb, long ldc,
                          float alpha, const float* bias, const float* rowscale, int epilogue, void* aux, long ldaux,
                          const int* m_live, const int* rowmap, editor_stream_t stream);

@@ -219,6 +219,7 @@ extern "C" int editor_bn1d_fwd(const float* x, long ldx, int B, int C, const flo
 extern "C" int editor_bn1d_bwd(const float* dy, const float* x, long ldx, int B, int C, const float* gamma,
     const float* save_mean, const float* save_invstd, float* dx, float* dgamma, float* dbeta, hipStream_t stream)
 {
+    if (B < 1 || C < 1) return (int)hipErrorInvalidValue;
     if (B <= 128)
         hipLaunchKernelGGL(bn1d_bwd_reg_kernel<32>, dim3((C + 63) / 64), dim3(256), 0, stream, dy, x, ldx, B, C, gamma, save_mean,
                            save_invstd, dx, dgamma, dbeta);

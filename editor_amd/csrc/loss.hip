@@ -85,6 +85,11 @@ __global__ void row_sqnorm_kernel(const float* __restrict__ f, long ldf, int D, 
 // one block per anchor: hardest positive (max distance among equal labels, self included as in the reference) and
 // hardest negative (min among different labels).  Ties resolve to the lowest index.
 // coef[i] = sigmoid(d_ap - d_an); coef[B+i] = 1/d_ap (0 where clamped); coef[2B+i] = 1/d_an.
+// Non-finite features (an overflowed f16 step): torch.clamp keeps a NaN and torch.max / torch.min return it, so an anchor with
+// a NaN distance among its positives (negatives) has d_ap (d_an) = NaN and a NaN loss; fmaxf alone would turn that distance
+// into 1e-6.  A NaN never wins the ordered comparisons of the search, so the indices come from the comparable distances only:
+// idx[i] (positive) always lies in [0, B) - it falls back to the anchor itself, which is its own positive, when every positive
+// distance is NaN - and idx[B+i] (negative) in [-1, B), -1 = no comparable negative (the backward skips that term).
 __global__ void triplet_mine_kernel(const float* __restrict__ gram, const float* __restrict__ sq,
     const long* __restrict__ label, int B, int* __restrict__ idx, float* __restrict__ coef, float* __restrict__ row_loss)
 {
@@ -95,12 +100,14 @@ __global__ void triplet_mine_kernel(const float* __restrict__ gram, const float*
     const float sqi = sq[i];
     float bp = -INFINITY, bn = INFINITY;
     int ip = -1, in_ = -1;
+    bool nanp = false, nann = false;
     for (int j = tid; j < B; j += blockDim.x) {
         const float q = sqi + sq[j] - 2.f * gram[(long)i * B + j];
-        const float d = sqrtf(fmaxf(q, 1e-12f));
-        if (label[j] == li) { if (d > bp) { bp = d; ip = j; } }
-        else                { if (d < bn) { bn = d; in_ = j; } }
+        const float d = q != q ? q : sqrtf(fmaxf(q, 1e-12f));
+        if (label[j] == li) { nanp |= q != q; if (d > bp) { bp = d; ip = j; } }
+        else                { nann |= q != q; if (d < bn) { bn = d; in_ = j; } }
     }
+    const int nan_any = __syncthreads_or((nanp ? 1 : 0) | (nann ? 2 : 0));
     sv[0][tid] = bp; si[0][tid] = ip; sv[1][tid] = bn; si[1][tid] = in_;
     __syncthreads();
     for (int o = blockDim.x >> 1; o > 0; o >>= 1) {
@@ -115,8 +122,8 @@ __global__ void triplet_mine_kernel(const float* __restrict__ gram, const float*
         __syncthreads();
     }
     if (tid == 0) {
-        const float ap = sv[0][0], an = sv[1][0];
-        const int p = si[0][0], n = si[1][0];
+        const float ap = (nan_any & 1) ? NAN : sv[0][0], an = (nan_any & 2) ? NAN : sv[1][0];
+        const int p = si[0][0] >= 0 ? si[0][0] : i, n = si[1][0];
         idx[i] = p; idx[B + i] = n;
         const float z = ap - an;                                         // SoftMarginLoss(an - ap, 1) = log(1 + e^z)
         row_loss[i] = z > 0.f ? z + log1pf(expf(-z)) : log1pf(expf(z));
@@ -191,6 +198,7 @@ __global__ __launch_bounds__(256) void triplet_bwd_kernel(const float* __restric
 // CenterLoss.forward (layers/center_loss.py:30-51): distmat[i,k] = |x_i|^2 + |c_k|^2 - 2 x_i . c_k (the expanded form the reference
 // computes with addmm_), masked to k = label_i, EVERY entry clamped to [1e-12, 1e12] - the B (C - 1) masked-out zeros each contribute
 // 1e-12 - summed and divided by B.  One workgroup per sample: row[i] = clamp(d_i) with d_i kept for the backward's clamp gate.
+// A NaN distance (non-finite features) stays NaN as under torch.clamp - fminf / fmaxf would return the bound instead.
 __global__ __launch_bounds__(256) void center_loss_fwd_kernel(const float* __restrict__ x, const float* __restrict__ centers,
     const long* __restrict__ label, int D, float* __restrict__ dist, float* __restrict__ row)
 {
@@ -206,7 +214,7 @@ __global__ __launch_bounds__(256) void center_loss_fwd_kernel(const float* __res
     if (threadIdx.x == 0) {
         const float d = (xx + cc) - 2.f * xc;
         dist[i] = d;
-        row[i] = fminf(fmaxf(d, 1e-12f), 1e12f);
+        row[i] = d != d ? d : fminf(fmaxf(d, 1e-12f), 1e12f);
     }
 }
 // dx_i = dloss * 2 (x_i - c_{y_i}) / B where d_i lies inside the clamp range, else 0
@@ -283,7 +291,7 @@ int editor_ce_smooth_bwd(const float* logits, const long* target, int B, int C, 
 int editor_triplet_fwd(const float* feat, long ldf, const long* label, int B, int D, float* gram, float* sq, int* idx,
                        float* coef, float* row_loss, float* loss, int accumulate, editor_stream_t stream)
 {
-    if (B <= 1 || D <= 0) return 1;
+    if (B <= 1 || B > 1024 || D <= 0) return 1;                      // (B > 1024: the backward's LDS list, refused here already)
     hipStream_t st = (hipStream_t)stream;
     row_sqnorm_kernel<<<B, 256, 0, st>>>(feat, ldf, D, sq);
     // gram = feat feat^T on the exact-fp32 matrix cores (B operand in the (N,K) nn.Linear layout = feat itself).  B x B

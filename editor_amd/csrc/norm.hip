@@ -641,6 +641,9 @@ __global__ __launch_bounds__(256) void embed_bwd_sie_kernel(const float* __restr
 // Block = D/4 threads (one 16-byte column group each), SFTS_ROWS consecutive token rows per block, the nmod loads of FOUR rows
 // requested before the first is used (the grid-stride form did two 64-bit divisions per 16 bytes and kept at most nmod
 // loads in flight: 3.7 TB/s on 304 MB).
+// The last wave of the block is partial when D/4 is not a multiple of 64 (D = 384: 96 threads, D = 196: 49).  block_sum's cross-lane
+// adds then name lanes the launch never started; ds_bpermute_b32 returns 0 for a lane that is off in EXEC, which is what a sum
+// needs (tests/test_gpu_head_edges.py::test_sfts_apply holds the loss at both widths).
 constexpr int SFTS_ROWS = 8;
 template <int NMOD>
 __global__ __launch_bounds__(256) void sfts_apply_kernel(const float* __restrict__ feat, const uint8_t* __restrict__ index,

@@ -375,7 +375,8 @@ int editor_pool_packed_bwd_nofill(const float* dout, const float* num, const int
 /* ---- head kernels ------------------------------------------------------------------------------------ */
 
 /* nn.BatchNorm1d on (B,C) rows with row stride ldx (make_model.py:115,120,140).  training: batch statistics, running
- * stats updated in place (momentum, unbiased variance); eval: running stats.  save_mean/save_invstd: (C), training only. */
+ * stats updated in place (momentum, unbiased variance); eval: running stats.  save_mean/save_invstd: (C), training only.
+ * Both directions refuse B < 1 or C < 1. */
 int editor_bn1d_fwd(const float* x, long ldx, int B, int C, const float* gamma, const float* beta, float* running_mean,
                     float* running_var, float momentum, float eps, int training, float* y, float* save_mean,
                     float* save_invstd, editor_stream_t stream);
@@ -393,7 +394,8 @@ int editor_ocfr_bwd(const float* fnorm, const float* inv_norm, const float* cent
 
 /* CenterLoss.forward (layers/center_loss.py:30-51): loss = sum over the (B, C) matrix [k == label_i] (|x_i|^2 + |c_k|^2 - 2 x_i.c_k), every
  * entry clamped to [1e-12, 1e12], / B.  x (B,D), centers (C,D) fp32, label (B) int64; dist (B) receives the unclamped own-class
- * distances (saved for the backward's clamp gate), row (B) is scratch.  Backward: dx (B,D) and / or dcenters (C,D) (either may be NULL). */
+ * distances (saved for the backward's clamp gate), row (B) is scratch.  A NaN distance (non-finite x or centre) stays NaN, as under
+ * torch.clamp: the loss is then NaN.  Backward: dx (B,D) and / or dcenters (C,D) (either may be NULL). */
 int editor_center_loss_fwd(const float* x, const float* centers, const long* label, int B, int C, int D, float* dist, float* row,
                            float* loss, editor_stream_t stream);
 int editor_center_loss_bwd(const float* x, const float* centers, const long* label, const float* dist, const float* dloss, int B, int C,
@@ -407,7 +409,10 @@ int editor_ce_smooth_bwd(const float* logits, const long* target, int B, int C, 
 /* TripletLoss() without margin (layers/triplet_loss.py:16-33,51-84,121-136): Euclidean distances with the 1e-12
  * clamp, batch-hard positive / negative per anchor, loss (+)= mean softplus(d_ap - d_an).  feat rows have stride ldf.
  * Scratch / saved for backward: gram (9,B,B: the Gram matrix + 8 reduction-chunk slabs), sq (B), idx (2B: positive,
- * negative), coef (3B), row_loss (B). */
+ * negative), coef (3B), row_loss (B).  2 <= B <= 1024 in both directions (the backward lists an anchor's partners in LDS).
+ * Non-finite features: a NaN distance is kept as torch.clamp keeps it, so every anchor that has one among its positives or its
+ * negatives gets a NaN loss (and coef); the indices come from the comparable distances only and stay usable: idx[i] in [0, B)
+ * (the anchor itself when no positive distance compares), idx[B+i] in [-1, B) (-1: no comparable negative, term skipped). */
 int editor_triplet_fwd(const float* feat, long ldf, const long* label, int B, int D, float* gram, float* sq, int* idx,
                        float* coef, float* row_loss, float* loss, int accumulate, editor_stream_t stream);
 int editor_triplet_bwd(const float* feat, long ldf, int B, int D, const int* idx, const float* coef, const float* dloss,

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import rel_err
+from edge_helpers import _NoCtx, _Poison, _boundary_rows, _check, _gelu64, _gelu_grad64, _gen, _randn, _up   # noqa: F401
 from editor_amd import config, functional as fn, ops, synth
 
 pytestmark = pytest.mark.gpu
@@ -22,10 +23,6 @@ M3 = 3 * B * T                  # 49 536: the headline's three modalities (208-r
 TOL16 = {torch.bfloat16: 4e-3, torch.float16: 5e-4}
 TOL32, TOL_WG, TOL_CS = 1e-5, 2e-5, 1e-5
 DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16}
-
-
-def _up(x, k):
-    return -(-x // k) * k
 
 
 def hazard_counts(b=B, t=T, th=208):
@@ -61,38 +58,6 @@ def test_tile_plan_takes_short_tiles_at_these_shapes():
         assert _up(nl * T, 208) < _up(nl * T, 64)
 
 
-class _Poison:
-    """torch.empty / torch.empty_like fill every floating-point CUDA allocation with NaN (integer and bool buffers are left alone:
-    an out-of-range index would fault the device, a NaN only shows up in a result)."""
-
-    def __init__(self, monkeypatch):
-        self.mp = monkeypatch
-
-    def __enter__(self):
-        real_empty, real_like = torch.empty, torch.empty_like
-
-        def fill(t):
-            if t.is_cuda and t.dtype.is_floating_point:
-                t.fill_(float("nan"))
-            return t
-        self.ctx = self.mp.context()
-        mp = self.ctx.__enter__()
-        mp.setattr(torch, "empty", lambda *a, **k: fill(real_empty(*a, **k)))
-        mp.setattr(torch, "empty_like", lambda *a, **k: fill(real_like(*a, **k)))
-        return self
-
-    def __exit__(self, *exc):
-        return self.ctx.__exit__(*exc)
-
-
-def _gen(seed):
-    return torch.Generator(device="cuda").manual_seed(seed)
-
-
-def _randn(shape, seed, std=1.0):
-    return torch.randn(*shape, generator=_gen(seed), device="cuda") * std
-
-
 def _keep(b, nl, seed):
     """bool (b,): exactly nl samples kept, at random positions"""
     k = torch.zeros(b, dtype=torch.bool)
@@ -113,37 +78,6 @@ def _plan(b, nl, seed, t=T):
     perm, inv, live = ops.droppath_plan(sc, 1, b, t)
     assert int(live[0, 1]) == nl * t
     return sc[0, 1].contiguous(), perm[0, 1].contiguous(), inv[0, 1].contiguous(), live[0, 1:2].contiguous()
-
-
-def _boundary_rows(live, m):
-    """rows of the tiles (208 and 256 rows) that hold row live - 1, live, roundup64(live) and the last row"""
-    rows = set()
-    for r in (live - 1, live, _up(live, 64), m - 1):
-        if 0 <= r < m:
-            for h in (208, 256):
-                rows.update(range(r // h * h, min(r // h * h + h, m)))
-    return sorted(rows)
-
-
-def _check(got, ref, tol, m, what):
-    """got / ref: the live rows (live, n); L2 and the worst per-row relative error of the boundary tiles' live rows"""
-    live = got.shape[0]
-    if live == 0:
-        return
-    e = rel_err(got, ref)
-    assert e < tol, (what, "L2", e)
-    rows = [r for r in _boundary_rows(live, m) if r < live]
-    g, r_ = got[rows].double(), ref[rows].double()
-    per = ((g - r_).norm(dim=1) / r_.norm(dim=1).clamp_min(1e-30)).max().item()
-    assert per < tol, (what, "worst boundary row", per)
-
-
-def _gelu64(x):
-    return 0.5 * x * (1.0 + torch.erf(x * 0.5 ** 0.5))
-
-
-def _gelu_grad64(x):
-    return 0.5 * (1.0 + torch.erf(x * 0.5 ** 0.5)) + x * torch.exp(-0.5 * x * x) * (2.0 * torch.pi) ** -0.5
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -543,14 +477,6 @@ def test_two_blocks_with_hazard_live_counts(mode, monkeypatch):
     for n, a_, b_ in zip(names, got[2], ref[2]):
         e = rel_err(a_, b_)
         assert e < _grad_tolerances(n), (mode, n, e)
-
-
-class _NoCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -1213,6 +1213,75 @@ extern "C" int editor_im2col16(const float* img, int B, int C, int H, int W, voi
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// PatchEmbed_overlap at any stride 1 <= s <= 16 (vit_pytorch.py:420-458): 16x16 windows at origin (py*sy, px*sx),
+// ny = (H-16)/sy + 1 by nx = (W-16)/sx + 1 of them; rows and columns laid out as im2col16_kernel writes them.
+// VL floats per load: a window's row starts at column px*sx + j4*4 of an image row, so 16-byte loads need sx % 4 == 0
+// (and W % 4 == 0, a 16-byte aligned image), sx = 14 / 10 / 6 / 2 keeps 8-byte loads and the odd strides load scalars.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+template <typename T, int VL>
+__global__ void im2col_patch_kernel(const float* __restrict__ img, int C, int H, int W, int sy, int sx, int ny, int nx,
+                                    long total4, T* __restrict__ out, T* __restrict__ out_lo)
+{
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total4; e += (long)gridDim.x * blockDim.x) {
+        const int j4 = (int)(e & 3);
+        uint32_t r = (uint32_t)(e >> 2);                      // (32-bit index arithmetic as in im2col16_kernel; host-checked)
+        const int i = (int)(r & 15u); r >>= 4;
+        const int c = (int)(r % (uint32_t)C); r /= (uint32_t)C;
+        const int p = (int)(r % (uint32_t)(ny * nx));
+        const int b = (int)(r / (uint32_t)(ny * nx));
+        const int y = (p / nx) * sy + i, x0 = (p % nx) * sx + j4 * 4;
+        const float* src = img + (((long)b * C + c) * H + y) * W + x0;
+        float4 v;
+        if constexpr (VL == 4) v = *reinterpret_cast<const float4*>(src);
+        else if constexpr (VL == 2) {
+            const float2 a = *reinterpret_cast<const float2*>(src), d = *reinterpret_cast<const float2*>(src + 2);
+            v = make_float4(a.x, a.y, d.x, d.y);
+        } else v = make_float4(src[0], src[1], src[2], src[3]);
+        const long o = ((long)b * ny * nx + p) * (C * 256) + c * 256 + i * 16 + j4 * 4;
+        if (out_lo) st_split(out + o, out_lo + o, v);
+        else Vec4<T>::st(out + o, v);
+    }
+}
+
+template <typename T>
+int im2col_patch_launch(const float* img, int B, int C, int H, int W, int sy, int sx, T* out, T* out_lo, hipStream_t stream)
+{
+    if (sy < 1 || sy > 16 || sx < 1 || sx > 16 || H < 16 || W < 16 || B <= 0 || C <= 0 || !img || !out)
+        return (int)hipErrorInvalidValue;
+    const int ny = (H - 16) / sy + 1, nx = (W - 16) / sx + 1;
+    const long total4 = (long)B * ny * nx * C * 64;
+    if (total4 >= (1L << 33)) return (int)hipErrorInvalidValue;          // (the kernel's row index is 32-bit: total4 / 4 < 2^31)
+    const uintptr_t a = reinterpret_cast<uintptr_t>(img);
+    const dim3 grid(grid_for(total4)), block(256);
+    if (sx % 4 == 0 && W % 4 == 0 && a % 16 == 0)
+        hipLaunchKernelGGL((im2col_patch_kernel<T, 4>), grid, block, 0, stream, img, C, H, W, sy, sx, ny, nx, total4, out, out_lo);
+    else if (sx % 2 == 0 && W % 2 == 0 && a % 8 == 0)
+        hipLaunchKernelGGL((im2col_patch_kernel<T, 2>), grid, block, 0, stream, img, C, H, W, sy, sx, ny, nx, total4, out, out_lo);
+    else
+        hipLaunchKernelGGL((im2col_patch_kernel<T, 1>), grid, block, 0, stream, img, C, H, W, sy, sx, ny, nx, total4, out, out_lo);
+    EDITOR_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int editor_im2col_patch(const float* img, int B, int C, int H, int W, int sy, int sx, void* out, int out_bf16,
+                                   hipStream_t stream)
+{
+    DISPATCH_T(out_bf16, return im2col_patch_launch<TT>(img, B, C, H, W, sy, sx, (TT*)out, (TT*)nullptr, stream));
+    return 0;
+}
+
+extern "C" int editor_im2col_patch_f16x2(const float* img, int B, int C, int H, int W, int sy, int sx, uint16_t* out_hi,
+                                         uint16_t* out_lo, hipStream_t stream)
+{
+    if (!out_hi || !out_lo) return (int)hipErrorInvalidValue;
+    return im2col_patch_launch<f16_t>(img, B, C, H, W, sy, sx, (f16_t*)out_hi, (f16_t*)out_lo, stream);
+}
+
 extern "C" int editor_embed_assemble(const void* patch, int patch_bf16, const float* cls, const float* pos,
     const float* sie, const long* cam, int Bcam, float coef, long Btot, int T, int D, float* x, hipStream_t stream)
 {

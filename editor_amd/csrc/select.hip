@@ -5,6 +5,7 @@
 //   K6    attention rollout: row-vector form r <- r * A_l, one workgroup per (sample, head)
 //   K10   SFTS mask apply + background-consistency loss (+ backward)
 // Reference behaviour restated: modeling/fusion_part/Frequency.py:42-84, SFTS.py:145-164,181-230.
+#include <type_traits>
 #include "common.h"
 #include "../../include/editor_hip.h"
 
@@ -60,10 +61,13 @@ __device__ __forceinline__ Quad gather_level(float v, int lane, int bx, int by) 
 // LDS with one 16-byte load per thread and plane (full cache lines): 54 us against 39 - 39 KiB of LDS per block leaves a
 // quarter of the waves resident, and the kernel is bound by its shuffle chains, not by request granularity.
 // NMOD == 0: the generic runtime-count form.
-template <int NMOD, int NC>
+// OUT = int32_t: one count per aligned tile.  OUT = uint16_t (overlapping windows, STRIDE_SIZE < 16): the tile's "> 0" bits instead,
+// one 16-bit row mask per (sample, image row, tile column) - bit j of plane[(b*H + y) * (W/16) + tx] is pixel (y, tx*16 + j) - for
+// freq_window_counts_kernel below; everything up to the comparison is the same code.
+template <int NMOD, int NC, typename OUT = int32_t>
 __global__ __launch_bounds__(256) void freq_counts_kernel(
     const float* __restrict__ m0, const float* __restrict__ m1, const float* __restrict__ m2, const float* __restrict__ m3,
-    int nmod_rt, int B, int C_rt, int H, int W, int32_t* __restrict__ counts)
+    int nmod_rt, int B, int C_rt, int H, int W, OUT* __restrict__ counts)
 {
     const int nmod = NMOD > 0 ? NMOD : nmod_rt, C = NMOD > 0 ? NC : C_rt;
     const int lane = threadIdx.x & 63;
@@ -140,9 +144,20 @@ __global__ __launch_bounds__(256) void freq_counts_kernel(
     }
     // sign(mean over channels) == sign(sum); torch.mean then .gt(0) (Frequency.py:44,54)
     const float cdiv = (float)C;
-    int cnt = ((sum[0] / cdiv) > 0.f) + ((sum[1] / cdiv) > 0.f) + ((sum[2] / cdiv) > 0.f) + ((sum[3] / cdiv) > 0.f);
-    cnt = wave_sum_i(cnt);
-    if (lane == 0) counts[tile] = cnt;
+    if constexpr (std::is_same<OUT, uint16_t>::value) {
+        // rows y0 / y0 + 1 of the tile in the low / high half; the 8 lanes of a lane row OR their 2-bit pieces together
+        uint32_t w = ((uint32_t)((sum[0] / cdiv) > 0.f) | ((uint32_t)((sum[1] / cdiv) > 0.f) << 1)) << (lx * 2);
+        w |= ((uint32_t)((sum[2] / cdiv) > 0.f) | ((uint32_t)((sum[3] / cdiv) > 0.f) << 1)) << (lx * 2 + 16);
+        w |= __shfl_xor(w, 1, 64); w |= __shfl_xor(w, 2, 64); w |= __shfl_xor(w, 4, 64);
+        if (lx == 0) {
+            counts[((long)b * H + y0) * tiles_x + tx] = (OUT)(w & 0xffffu);
+            counts[((long)b * H + y0 + 1) * tiles_x + tx] = (OUT)(w >> 16);
+        }
+    } else {
+        int cnt = ((sum[0] / cdiv) > 0.f) + ((sum[1] / cdiv) > 0.f) + ((sum[2] / cdiv) > 0.f) + ((sum[3] / cdiv) > 0.f);
+        cnt = wave_sum_i(cnt);
+        if (lane == 0) counts[tile] = cnt;
+    }
 }
 
 // ---- round 4: 4 x 4 pixels per lane ------------------------------------------------------------------------------------
@@ -187,10 +202,10 @@ template <int DIV> __device__ __forceinline__ float div_small(float x, bool& rar
     }
 }
 
-template <int NMOD, int NC>
+template <int NMOD, int NC, typename OUT = int32_t>           // OUT: as freq_counts_kernel (int32_t counts / uint16_t row masks)
 __global__ __launch_bounds__(256) void freq_counts4_kernel(
     const float* __restrict__ m0, const float* __restrict__ m1, const float* __restrict__ m2, const float* __restrict__ m3,
-    int B, int H, int W, int32_t* __restrict__ counts)
+    int B, int H, int W, OUT* __restrict__ counts)
 {
     const int lane = threadIdx.x & 63;
     const int tiles_x = W >> 4, tiles_y = H >> 4, ntile = tiles_x * tiles_y;
@@ -294,15 +309,81 @@ __global__ __launch_bounds__(256) void freq_counts4_kernel(
 #pragma unroll
         for (int i = 0; i < 16; ++i) mean[i] = sum[i >> 2][i & 3] / (float)NC;
     }
-    int cnt = 0;
+    if constexpr (std::is_same<OUT, uint16_t>::value) {
+        // the lane's rows 0, 1 in the halves of w0 and rows 2, 3 in w1; the 4 lanes of a lane row OR their nibbles together
+        uint32_t w0 = 0, w1 = 0;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) cnt += mean[i] > 0.f;
-    // sum over the 16 lanes of the patch
-    cnt += __builtin_amdgcn_mov_dpp(cnt, 0xB1, 0xF, 0xF, true);
-    cnt += __builtin_amdgcn_mov_dpp(cnt, 0x4E, 0xF, 0xF, true);
-    cnt += __builtin_amdgcn_ds_swizzle(cnt, 0x1F | (4 << 10));
-    cnt += __builtin_amdgcn_ds_swizzle(cnt, 0x1F | (8 << 10));
-    if ((lane & 15) == 0 && tile_raw < total) counts[tile] = cnt;
+        for (int j = 0; j < 4; ++j) {
+            w0 |= (uint32_t)(mean[j] > 0.f) << j | (uint32_t)(mean[4 + j] > 0.f) << (16 + j);
+            w1 |= (uint32_t)(mean[8 + j] > 0.f) << j | (uint32_t)(mean[12 + j] > 0.f) << (16 + j);
+        }
+        w0 <<= lx * 4; w1 <<= lx * 4;
+        auto quad_or = [](uint32_t v) {                    // OR over the 4 lanes of a lane row (DPP quad permutes: xor 1, xor 2)
+            v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);
+            v |= (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);
+            return v;
+        };
+        w0 = quad_or(w0); w1 = quad_or(w1);
+        if (lx == 0 && tile_raw < total) {
+            OUT* dst = counts + ((long)b * H + y0) * tiles_x + tx;
+            dst[0] = (OUT)(w0 & 0xffffu); dst[tiles_x] = (OUT)(w0 >> 16);
+            dst[2 * tiles_x] = (OUT)(w1 & 0xffffu); dst[3 * tiles_x] = (OUT)(w1 >> 16);
+        }
+    } else {
+        int cnt = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) cnt += mean[i] > 0.f;
+        // sum over the 16 lanes of the patch
+        cnt += __builtin_amdgcn_mov_dpp(cnt, 0xB1, 0xF, 0xF, true);
+        cnt += __builtin_amdgcn_mov_dpp(cnt, 0x4E, 0xF, 0xF, true);
+        cnt += __builtin_amdgcn_ds_swizzle(cnt, 0x1F | (4 << 10));
+        cnt += __builtin_amdgcn_ds_swizzle(cnt, 0x1F | (8 << 10));
+        if ((lane & 15) == 0 && tile_raw < total) counts[tile] = cnt;
+    }
+}
+
+// Overlapping windows: count of set bits of the 16 x 16 window at origin (py*s, px*s) of the row-mask plane the kernels above
+// write with OUT = uint16_t.  16 lanes per window, one per row: a window row spans at most two adjacent 16-bit words.
+__global__ __launch_bounds__(256) void freq_window_counts_kernel(const uint16_t* __restrict__ plane, int B, int H, int tiles_x,
+                                                                 int s, int ny, int nx, int32_t* __restrict__ counts)
+{
+    const long total = (long)B * ny * nx;
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int r = (int)(gid & 15);
+    const long win_raw = gid >> 4;
+    const long win = win_raw < total ? win_raw : total - 1;       // (a clamped slot never writes)
+    const int b = (int)(win / (ny * nx)), p = (int)(win % (ny * nx));
+    const int y = (p / nx) * s + r, x = (p % nx) * s;
+    const int tx = x >> 4, sh = x & 15;
+    const uint16_t* row = plane + ((long)b * H + y) * tiles_x;
+    uint32_t w = row[tx];
+    if (sh) w |= (uint32_t)row[tx + 1] << 16;                     // (x + 15 < W: the window's last column lies in word tx + 1)
+    int cnt = __popc((w >> sh) & 0xffffu);
+    cnt += __shfl_xor(cnt, 1, 64); cnt += __shfl_xor(cnt, 2, 64); cnt += __shfl_xor(cnt, 4, 64); cnt += __shfl_xor(cnt, 8, 64);
+    if (r == 0 && win_raw < total) counts[win] = cnt;
+}
+
+static int freq_counts_stride_launch(const float* m0, const float* m1, const float* m2, const float* m3, int nmod, int B, int C, int H,
+                                     int W, int s, uint16_t* plane, int32_t* counts, hipStream_t stream)
+{
+    if ((H & 15) || (W & 15) || B <= 0 || C <= 0 || s < 1 || s > 16 || !plane || !counts) return (int)hipErrorInvalidValue;
+    const long tiles = (long)B * (H >> 4) * (W >> 4);
+    const dim3 grid((unsigned)((tiles + 3) / 4)), grid4((unsigned)((tiles + 15) / 16)), block(256);
+    const bool al16 = ((reinterpret_cast<uintptr_t>(m0) | reinterpret_cast<uintptr_t>(m1) | reinterpret_cast<uintptr_t>(m2) |
+                        reinterpret_cast<uintptr_t>(m3)) & 15) == 0;
+    if (nmod == 3 && C == 3 && al16)
+        hipLaunchKernelGGL((freq_counts4_kernel<3, 3, uint16_t>), grid4, block, 0, stream, m0, m1, m2, m3, B, H, W, plane);
+    else if (nmod == 4 && C == 3 && al16)
+        hipLaunchKernelGGL((freq_counts4_kernel<4, 3, uint16_t>), grid4, block, 0, stream, m0, m1, m2, m3, B, H, W, plane);
+    else
+        hipLaunchKernelGGL((freq_counts_kernel<0, 0, uint16_t>), grid, block, 0, stream, m0, m1, m2, m3, nmod, B, C, H, W, plane);
+    EDITOR_LAUNCH_CHECK();
+    const int ny = (H - 16) / s + 1, nx = (W - 16) / s + 1;
+    const long lanes = (long)B * ny * nx * 16;
+    hipLaunchKernelGGL(freq_window_counts_kernel, dim3((unsigned)((lanes + 255) / 256)), block, 0, stream, plane, B, H, W >> 4, s, ny, nx,
+                       counts);
+    EDITOR_LAUNCH_CHECK();
+    return 0;
 }
 
 static int freq_counts_launch(const float* m0, const float* m1, const float* m2, const float* m3, int nmod, int B, int C, int H, int W,
@@ -549,6 +630,21 @@ extern "C" int editor_freq_counts_nmod_f32(const float* m0, const float* m1, con
     if ((H & 15) || (W & 15) || B <= 0 || C <= 0 || nmod < 2 || nmod > 4 || !m0 || !m1 || (nmod > 2 && !m2) || (nmod > 3 && !m3))
         return (int)hipErrorInvalidValue;
     return freq_counts_launch(m0, m1, m2, m3, nmod, B, C, H, W, counts, stream);
+}
+
+extern "C" int editor_freq_counts_stride_f32(const float* rgb, const float* nir, const float* tir, int B, int C, int H, int W,
+                                             int stride, uint16_t* plane, int32_t* counts, hipStream_t stream)
+{
+    if (!rgb || !nir) return (int)hipErrorInvalidValue;
+    return freq_counts_stride_launch(rgb, nir, tir, nullptr, tir ? 3 : 2, B, C, H, W, stride, plane, counts, stream);
+}
+
+extern "C" int editor_freq_counts_stride_nmod_f32(const float* m0, const float* m1, const float* m2, const float* m3, int nmod,
+                                                  int B, int C, int H, int W, int stride, uint16_t* plane, int32_t* counts,
+                                                  hipStream_t stream)
+{
+    if (nmod < 2 || nmod > 4 || !m0 || !m1 || (nmod > 2 && !m2) || (nmod > 3 && !m3)) return (int)hipErrorInvalidValue;
+    return freq_counts_stride_launch(m0, m1, m2, m3, nmod, B, C, H, W, stride, plane, counts, stream);
 }
 
 template <typename V>

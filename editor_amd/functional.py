@@ -813,25 +813,26 @@ def _scaled_cast(dx, rowscale, dtype, m_live=None, gs=1.0):
 
 
 class PatchEmbedFn(torch.autograd.Function):
-    """PatchEmbed_overlap (vit_pytorch.py:449-458) + cls/pos/SIE assembly (:625-637) for stride 16.
-    img (Btot,3,H,W) fp32 (modalities stacked on the batch axis), cam (Bcam) int64."""
+    """PatchEmbed_overlap (vit_pytorch.py:449-458) + cls/pos/SIE assembly (:625-637): 16x16 windows at `stride` (sy, sx) <= 16.
+    img (Btot,3,H,W) fp32 (modalities stacked on the batch axis), cam (Bcam) int64.  The backward needs the saved im2col rows
+    only - one per window, whatever the stride."""
 
     @staticmethod
-    def forward(ctx, img, conv_w, conv_b, cls, pos, sie, cam, coef, act_dtype):
+    def forward(ctx, img, conv_w, conv_b, cls, pos, sie, cam, coef, act_dtype, stride=(16, 16)):
         # img: the stacked (Btot,3,H,W) batch, or the list of per-modality (B,3,H,W) tensors (no stacking copy)
         btot = sum(i.shape[0] for i in img) if isinstance(img, (list, tuple)) else img.shape[0]
         d = conv_w.shape[0]
         kdim = conv_w[0].numel()
         if act_dtype == F16X2:          # split-precision forward: fp32 patch rows from the half pairs; the backward is f16
             act_dtype = torch.float16
-            cols, cols_lo = ops.im2col16_split(img)
+            cols, cols_lo = ops.im2col_patch_split(img, stride)
             wh, wl = act_weight_split(conv_w)
             patch = torch.empty(cols.shape[0], d, dtype=torch.float32, device=cols.device)
             ops.gemm_split((cols, cols_lo), (wh.view(d, kdim), wl.view(d, kdim)), patch, None, cols.shape[0], d, kdim,
                            alpha=1.0 / ops.SPLIT_WSCALE, bias=conv_b)
             del cols_lo
         else:
-            cols = ops.im2col16(img, act_dtype)
+            cols = ops.im2col_patch(img, act_dtype, stride)
             w = act_weight(conv_w, act_dtype).view(d, kdim)
             patch = _linear_fwd(cols, w, conv_b, act_dtype)
         t = pos.shape[1]
@@ -860,7 +861,7 @@ class PatchEmbedFn(torch.autograd.Function):
         db = ops.colsum(dpatch, scale=1.0 / gs)
         dcls = dpos[0].clone().view(cls_shape)
         return (None, dw.view(conv_w.shape), db, dcls, dpos.view(pos_shape),
-                None if dsie is None else dsie.view(sie_shape), None, None, None)
+                None if dsie is None else dsie.view(sie_shape), None, None, None, None)
 
 
 class LayerNormFn(torch.autograd.Function):

@@ -90,9 +90,9 @@ class _Block(nn.Module):
 
 
 class _PatchEmbed(nn.Module):
-    def __init__(self, embed_dim):
+    def __init__(self, embed_dim, stride=(16, 16)):
         super().__init__()
-        self.proj = nn.Conv2d(3, embed_dim, kernel_size=16, stride=16)
+        self.proj = nn.Conv2d(3, embed_dim, kernel_size=16, stride=tuple(stride))
 
 
 def _init_linear_ln(mod):
@@ -110,14 +110,17 @@ class Trans(nn.Module):
     """Parameter layout of the reference's ViT `Trans` (vit_pytorch.py:461-534)."""
 
     def __init__(self, img_size, embed_dim, depth, heads, mlp_ratio, qkv_bias, camera, sie_xishu, drop_path_rate,
-                 qk_scale=None):
+                 qk_scale=None, stride=(16, 16)):
         super().__init__()
         self.embed_dim, self.depth, self.heads = embed_dim, depth, heads
         self.qk_scale = qk_scale
-        self.num_y, self.num_x = img_size[0] // 16, img_size[1] // 16
+        self.stride = (int(stride[0]), int(stride[1]))
+        # PatchEmbed_overlap (vit_pytorch.py:429-430): 16x16 windows at the stride; img // 16 when the stride is 16
+        self.num_y = (img_size[0] - 16) // self.stride[0] + 1
+        self.num_x = (img_size[1] - 16) // self.stride[1] + 1
         self.num_patches = self.num_y * self.num_x
         self.img_size = tuple(img_size)
-        self.patch_embed = _PatchEmbed(embed_dim)
+        self.patch_embed = _PatchEmbed(embed_dim, self.stride)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, self.num_patches + 1, embed_dim))
         self.cam_num = camera
@@ -178,9 +181,31 @@ class build_transformer(nn.Module):
         self.token_dim = dim
         cams = camera_num if cfg.MODEL.SIE_CAMERA else 0
         self.base = Trans(cfg.INPUT.SIZE_TRAIN, dim, depth, heads, mlp_ratio, qkv_bias, cams, cfg.MODEL.SIE_COE,
-                          cfg.MODEL.DROP_PATH, qk_scale)
+                          cfg.MODEL.DROP_PATH, qk_scale, stride_of(cfg))
         if cfg.MODEL.PRETRAIN_CHOICE == "imagenet":
             self.base.load_param(cfg.MODEL.PRETRAIN_PATH_T)
+
+
+def stride_of(cfg):
+    """cfg.MODEL.STRIDE_SIZE as (sy, sx); an int means both (to_2tuple, vit_pytorch.py:428)."""
+    st = cfg.MODEL.STRIDE_SIZE
+    return (int(st), int(st)) if isinstance(st, int) else (int(st[0]), int(st[1]))
+
+
+def check_stride(img_size, stride):
+    """The patch strides EDITOR supports are the ones the reference itself runs.  Its patch embedding makes (H-16)//s + 1 by
+    (W-16)//s + 1 windows (vit_pytorch.py:429-430), its head and its frequency mask size everything by H//s by W//s
+    (make_model.py:91, Frequency.py:46-61) and the frequency mask unfolds at STRIDE_SIZE[0] in both directions: where the two
+    counts differ, or the stride is not square, the reference fails inside its own mask()."""
+    h, w = int(img_size[0]), int(img_size[1])
+    sy, sx = stride
+    ok = sy == sx and 1 <= sy <= 16 and h >= 16 and w >= 16 and (h - 16) // sy + 1 == h // sy and (w - 16) // sx + 1 == w // sx
+    if not ok:
+        raise NotImplementedError(
+            "MODEL.STRIDE_SIZE %r at INPUT.SIZE_TRAIN %r: supported is a square stride s <= 16 with (H-16)//s + 1 == H//s and "
+            "(W-16)//s + 1 == W//s (at 256x128 and 128x256: s = 12 .. 16) - the settings the reference's own frequency mask runs"
+            % (list(stride), [h, w]))
+    return sy
 
 
 class _Wavelet(nn.Module):
@@ -201,12 +226,10 @@ class FrequencyIndex(nn.Module):
         self.DWT = _Wavelet(["h0_col", "h1_col", "h0_row", "h1_row"])
         self.IDWT = _Wavelet(["g0_col", "g1_col", "g0_row", "g1_row"])
         self.keep = int(keep)
-        self.stride = stride
-        if stride != 16:
-            raise NotImplementedError("the HIP frequency kernel tiles 16x16 windows (STRIDE_SIZE 16)")
+        self.stride = int(stride)          # 16x16 windows at this stride (Frequency.py:52); below 16 they overlap
 
     def forward(self, x, y, z=None, w=None, **_):
-        mask, _ = ops.frequency_mask(x, y, z, self.keep, w)
+        mask, _ = ops.frequency_mask(x, y, z, self.keep, w, self.stride)
         return mask.bool()
 
 
@@ -249,13 +272,14 @@ def _block_args(norm1, attn, norm2, mlp):
 class EDITOR(nn.Module):
     def __init__(self, num_classes, cfg, camera_num):
         super().__init__()
+        check_stride(cfg.INPUT.SIZE_TRAIN, stride_of(cfg))
         self.BACKBONE = build_transformer(num_classes, cfg, camera_num)
         dim = self.BACKBONE.token_dim
-        self.num_patches = (cfg.INPUT.SIZE_TRAIN[0] // cfg.MODEL.STRIDE_SIZE[0]) * \
-                           (cfg.INPUT.SIZE_TRAIN[1] // cfg.MODEL.STRIDE_SIZE[1])
+        stride = stride_of(cfg)
+        self.num_patches = (cfg.INPUT.SIZE_TRAIN[0] // stride[0]) * (cfg.INPUT.SIZE_TRAIN[1] // stride[1])
         self.ratio = (1 / self.num_patches) * int(cfg.MODEL.HEAD_KEEP)           # make_model.py:92
         self.head_k = int(self.num_patches * self.ratio)                        # SFTS.py:155
-        self.FREQ_INDEX = FrequencyIndex(cfg.MODEL.FREQUENCY_KEEP, cfg.MODEL.STRIDE_SIZE[0])
+        self.FREQ_INDEX = FrequencyIndex(cfg.MODEL.FREQUENCY_KEEP, stride[0])
         self.hma_heads = getattr(cfg.MODEL, "HMA_HEADS", 12 if dim % 12 == 0 else 16)    # make_model.py:97
         nmod = int(getattr(cfg.MODEL, "NUM_MODALITIES", 3))
         if nmod not in (3, 4):
@@ -388,7 +412,7 @@ class EDITOR(nn.Module):
         sie = base.sie_embed if base.cam_num > 1 else None
         x = fn.PatchEmbedFn.apply(imgs, base.patch_embed.proj.weight, base.patch_embed.proj.bias, base.cls_token,
                                   base.pos_embed, sie, cam if sie is not None else None, float(base.sie_xishu),
-                                  self.fn_dtype)
+                                  self.fn_dtype, base.stride)
         # softmax outputs of every layer; rows padded to a multiple of 4 floats in bf16 mode (16-byte stores)
         # f32 parity mode: the (L,3B,h,T,T) softmax outputs are materialised as the reference does.  bf16 mode: every
         # block hands back its (qkv, row log-sum-exp) instead and the rollout recomputes the probabilities from them
@@ -557,7 +581,8 @@ class EDITOR(nn.Module):
         side = fn._side_stream(rgb.device)
         side.wait_stream(cur)
         with torch.no_grad(), torch.cuda.stream(side):
-            mask_fre, _ = ops.frequency_mask(mods[0], mods[1], mods[2], self.FREQ_INDEX.keep, mods[3] if nmod > 3 else None)
+            mask_fre, _ = ops.frequency_mask(mods[0], mods[1], mods[2], self.FREQ_INDEX.keep, mods[3] if nmod > 3 else None,
+                                             self.FREQ_INDEX.stride)
             fre_done = side.record_event()
         feats, probs = self._backbone(mods, cam_label)
         t = feats.shape[1]

@@ -15,9 +15,28 @@ _raw_stream = _lib._raw_stream
 # ---------------------------------------------------------------------------------------------
 # token selection
 # ---------------------------------------------------------------------------------------------
-def freq_counts(rgb, nir, tir, m4=None):
-    """Frequency.py:65-84,42-56 -> (B, N) int32 positive-pixel counts per 16x16 patch (m4: 4-modal extension)."""
+def patch_grid(h, w, sy, sx=None):
+    """PatchEmbed_overlap's window grid (vit_pytorch.py:427-428): 16x16 windows at stride (sy, sx)."""
+    sx = sy if sx is None else sx
+    return (h - 16) // sy + 1, (w - 16) // sx + 1
+
+
+def freq_counts(rgb, nir, tir, m4=None, stride=16):
+    """Frequency.py:65-84,42-56 -> (B, N) int32 positive-pixel counts per 16x16 patch (m4: 4-modal extension).
+    stride < 16: the windows overlap (origin (py*stride, px*stride)); the aligned-tile kernel then leaves its "> 0" bits in a
+    scratch plane and a second launch counts the windows."""
     b, c, h, w = rgb.shape
+    if stride != 16:
+        ny, nx = patch_grid(h, w, stride)
+        counts = torch.empty(b, ny * nx, dtype=torch.int32, device=rgb.device)
+        plane = torch.empty(b * h * (w // 16), dtype=torch.int16, device=rgb.device)
+        if m4 is not None:
+            call("editor_freq_counts_stride_nmod_f32", rgb.contiguous(), nir.contiguous(), tir.contiguous(), m4.contiguous(), 4,
+                 b, c, h, w, int(stride), plane, counts)
+        else:
+            call("editor_freq_counts_stride_f32", rgb.contiguous(), nir.contiguous(),
+                 None if tir is None else tir.contiguous(), b, c, h, w, int(stride), plane, counts)
+        return counts
     counts = torch.empty(b, (h // 16) * (w // 16), dtype=torch.int32, device=rgb.device)
     if m4 is not None:
         call("editor_freq_counts_nmod_f32", rgb.contiguous(), nir.contiguous(), tir.contiguous(), m4.contiguous(), 4,
@@ -41,8 +60,8 @@ def topk_mask(vals, k, group=1):
     return mask
 
 
-def frequency_mask(rgb, nir, tir, keep, m4=None):
-    counts = freq_counts(rgb, nir, tir, m4)
+def frequency_mask(rgb, nir, tir, keep, m4=None, stride=16):
+    counts = freq_counts(rgb, nir, tir, m4, stride)
     return topk_mask(counts, keep), counts
 
 
@@ -375,6 +394,23 @@ def im2col16(img, dtype):
     return out
 
 
+def im2col_patch(img, dtype, stride):
+    """im2col16 for 16x16 windows at stride (sy, sx) <= 16 (PatchEmbed_overlap, vit_pytorch.py:420-458); stride 16 IS im2col16."""
+    sy, sx = stride
+    if sy == 16 and sx == 16:
+        return im2col16(img, dtype)
+    imgs = list(img) if isinstance(img, (list, tuple)) else [img]
+    b, c, h, w = imgs[0].shape
+    ny, nx = patch_grid(h, w, sy, sx)
+    rows = b * ny * nx
+    out = torch.empty(len(imgs) * rows, c * 256, dtype=dtype, device=imgs[0].device)
+    for i, im in enumerate(imgs):
+        if tuple(im.shape) != (b, c, h, w):
+            raise ValueError("im2col_patch: modality tensors of different shapes")
+        call("editor_im2col_patch", im, b, c, h, w, int(sy), int(sx), _ptr(out, i * rows * c * 256), _is_bf16(out))
+    return out
+
+
 def embed_assemble(patch, cls, pos, sie, cam, coef, btot, t, d):
     x = torch.empty(btot, t, d, dtype=torch.float32, device=patch.device)
     call("editor_embed_assemble", patch, _is_bf16(patch), cls, pos, sie, cam, 0 if cam is None else cam.numel(),
@@ -614,6 +650,23 @@ def im2col16_split(img):
         if tuple(im.shape) != (b, c, h, w):
             raise ValueError("im2col16: modality tensors of different shapes")
         call("editor_im2col16_f16x2", im, b, c, h, w, _ptr(hi, i * rows * c * 256), _ptr(lo, i * rows * c * 256))
+    return hi, lo
+
+
+def im2col_patch_split(img, stride):
+    sy, sx = stride
+    if sy == 16 and sx == 16:
+        return im2col16_split(img)
+    imgs = list(img) if isinstance(img, (list, tuple)) else [img]
+    b, c, h, w = imgs[0].shape
+    ny, nx = patch_grid(h, w, sy, sx)
+    rows = b * ny * nx
+    hi = torch.empty(len(imgs) * rows, c * 256, dtype=torch.float16, device=imgs[0].device)
+    lo = torch.empty_like(hi)
+    for i, im in enumerate(imgs):
+        if tuple(im.shape) != (b, c, h, w):
+            raise ValueError("im2col_patch: modality tensors of different shapes")
+        call("editor_im2col_patch_f16x2", im, b, c, h, w, int(sy), int(sx), _ptr(hi, i * rows * c * 256), _ptr(lo, i * rows * c * 256))
     return hi, lo
 
 

@@ -70,6 +70,18 @@ int editor_freq_counts_f32(const float* rgb, const float* nir, const float* tir,
 int editor_freq_counts_nmod_f32(const float* m0, const float* m1, const float* m2, const float* m3, int nmod, int B, int C,
                                 int H, int W, int32_t* counts, editor_stream_t stream);
 
+/* MODEL.STRIDE_SIZE = [s, s] below 16 (Frequency.py:42-56 with self.stride = s): the same reconstruction - Haar J = 4 in zero mode
+ * is local to ALIGNED 16x16 tiles, so every pixel's sign is the one the entry points above count - then the count of > 0 pixels
+ * of every 16x16 window at origin (py*s, px*s), ny = (H-16)/s + 1 by nx = (W-16)/s + 1 windows, row-major.  Two launches: the
+ * tile kernel writes one 16-bit "> 0" row mask per (sample, image row, tile column) into `plane` (B*H*(W/16) uint16, caller's
+ * scratch; the reconstructed image itself never reaches memory), a popcount kernel sums the windows.  1 <= s <= 16 (s = 16
+ * equals editor_freq_counts_f32); H, W multiples of 16.  counts: (B, ny*nx) int32. */
+int editor_freq_counts_stride_f32(const float* rgb, const float* nir, const float* tir, int B, int C, int H, int W, int stride,
+                                  uint16_t* plane, int32_t* counts, editor_stream_t stream);
+int editor_freq_counts_stride_nmod_f32(const float* m0, const float* m1, const float* m2, const float* m3, int nmod, int B,
+                                       int C, int H, int W, int stride, uint16_t* plane, int32_t* counts,
+                                       editor_stream_t stream);
+
 /* torch.topk(k) -> sort -> scatter_ to a bool row (Frequency.py:58-62, SFTS.py:155-158) with torch's CPU tie
  * order (libstdc++ partial_sort if k*64<=n else nth_element).  vals: (rows,n); `group` consecutive rows OR
  * into one mask row (SFTS.py:159-162: OR over heads); mask: (rows/group, n) uint8, fully overwritten. */
@@ -172,6 +184,13 @@ int editor_split_f32(const float* in, uint16_t* hi, uint16_t* lo, long n, float 
 
 /* PatchEmbed_overlap with stride == patch == 16 (vit_pytorch.py:449-458): im2col rows (b*N+p), cols (c,i,j). */
 int editor_im2col16(const float* img, int B, int C, int H, int W, void* out, int out_bf16, editor_stream_t stream);
+/* PatchEmbed_overlap at any stride 1 <= sy, sx <= 16 (vit_pytorch.py:420-458): 16x16 windows at origin (py*sy, px*sx),
+ * ny = (H-16)/sy + 1 by nx = (W-16)/sx + 1 per image; rows (b*ny*nx + p), cols (c,i,j) as editor_im2col16 (which it equals at
+ * stride 16).  hipErrorInvalidValue for a stride outside 1..16 or H, W < 16.  _f16x2: the split-precision half pair. */
+int editor_im2col_patch(const float* img, int B, int C, int H, int W, int sy, int sx, void* out, int out_bf16,
+                        editor_stream_t stream);
+int editor_im2col_patch_f16x2(const float* img, int B, int C, int H, int W, int sy, int sx, uint16_t* out_hi, uint16_t* out_lo,
+                              editor_stream_t stream);
 /* cls token + pos_embed + SIE_COE * sie_embed[cam] (vit_pytorch.py:627-637).  Btot samples may hold several
  * modalities stacked on the batch axis sharing `cam` (length Bcam): cam index = b % Bcam.  sie may be NULL. */
 int editor_embed_assemble(const void* patch, int patch_bf16, const float* cls, const float* pos, const float* sie,

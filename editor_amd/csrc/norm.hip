@@ -827,27 +827,27 @@ extern "C" int editor_resid_add_layernorm_fwd(const float* x, const void* branch
 }
 
 namespace {
+// Two-stage producer: the partial rows stay in `parts` ([P][2][D] dgamma | dbeta rows at its start; with want_colsum the cast
+// output's column sums [P][D] behind ws_rows*2*D floats), *nparts = P, and the caller folds them (editor_reduce_rows / _multi).
+// parts == NULL (plain form only): no parameter gradients.
 int layernorm_bwd_impl(const void* dy, int dy_bf16, float dy_scale, const float* x, const float* gamma, const float* mean,
-    const float* rstd, long M, int D, const uint8_t* rowmask, int mask_period, const float* dx_in, float* dx_out,
-    float* dgamma, float* dbeta, float* workspace, int ws_rows, const int* m_live, void* cast_out, const float* cast_rowscale,
-    float cast_scale, float* cast_colsum, float cast_colsum_scale, hipStream_t stream, int* nparts = nullptr,
-    const int* dy_perm = nullptr, const int* dy_live = nullptr, const int* cast_perm = nullptr)
+    const float* rstd, long M, int D, const uint8_t* rowmask, int mask_period, const float* dx_in, float* dx_out, float* parts,
+    int ws_rows, const int* m_live, void* cast_out, const float* cast_rowscale, float cast_scale, int want_colsum,
+    const int* dy_perm, const int* dy_live, const int* cast_perm, int* nparts, hipStream_t stream)
 {
-    // nparts != NULL: the "_parts" form - the partial rows stay in the workspace ([P][2][D] at its start, the cast output's column
-    // sums [P][D] behind ws_rows*2*D floats), *nparts = P, and the caller folds them (editor_reduce_rows_multi)
-    if (D % 4 || D > 1024 || M <= 0 || ws_rows < 1) return (int)hipErrorInvalidValue;
-    if (cast_out && (dy_bf16 == 0 || m_live || rowmask || D % 256)) return (int)hipErrorInvalidValue;    // dense 16-bit rows only
+    if (D % 4 || D > 1024 || M <= 0 || ws_rows < 1 || !nparts) return (int)hipErrorInvalidValue;
+    if (cast_out && (dy_bf16 == 0 || m_live || rowmask || D % 256 || !parts)) return (int)hipErrorInvalidValue;  // dense 16-bit rows only
     long blocks = (M + 3) / 4;
     if (blocks > ws_rows) blocks = ws_rows;
-    float* cast_partials = (cast_out && cast_colsum) ? workspace + (long)ws_rows * 2 * D : nullptr;   // third [ws_rows][D] region
+    float* cast_partials = (cast_out && want_colsum) ? parts + (long)ws_rows * 2 * D : nullptr;   // third [ws_rows][D] region
 #define LN_BWD_LAUNCH(NVv, CASTv) DISPATCH_T(dy_bf16, hipLaunchKernelGGL((layernorm_bwd_kernel<TT, NVv, CASTv>), dim3((unsigned)blocks), \
         dim3(256), 0, stream, (const TT*)dy, x, gamma, mean, rstd, M, D, rowmask, mask_period, dx_in, dx_out,                            \
-        dgamma ? workspace : nullptr, m_live, dy_scale, (TT*)cast_out, cast_rowscale, cast_scale, cast_partials))
+        parts, m_live, dy_scale, (TT*)cast_out, cast_rowscale, cast_scale, cast_partials))
     if (dy_perm || cast_perm) {          // compacted rows (stochastic depth): the cast form on dense 16-bit rows, D = 768 / 1024
         if (!cast_out || (dy_perm && !dy_live)) return (int)hipErrorInvalidValue;
 #define LN_BWD_PERM(NVv) DISPATCH_T(dy_bf16, hipLaunchKernelGGL((layernorm_bwd_kernel<TT, NVv, true, false, true>), dim3((unsigned)blocks), \
         dim3(256), 0, stream, (const TT*)dy, x, gamma, mean, rstd, M, D, rowmask, mask_period, dx_in, dx_out,                            \
-        dgamma ? workspace : nullptr, m_live, dy_scale, (TT*)cast_out, cast_rowscale, cast_scale, cast_partials, dy_perm, dy_live, cast_perm))
+        parts, m_live, dy_scale, (TT*)cast_out, cast_rowscale, cast_scale, cast_partials, dy_perm, dy_live, cast_perm))
         switch (D >> 8) {
             case 1: LN_BWD_PERM(1); break;
             case 2: LN_BWD_PERM(2); break;
@@ -859,7 +859,7 @@ int layernorm_bwd_impl(const void* dy, int dy_bf16, float dy_scale, const float*
     if (D % 256) {                       // ragged width (384): guarded instantiations, no cast output
 #define LN_BWD_RAGGED(NVv) DISPATCH_T(dy_bf16, hipLaunchKernelGGL((layernorm_bwd_kernel<TT, NVv, false, true>), dim3((unsigned)blocks), \
         dim3(256), 0, stream, (const TT*)dy, x, gamma, mean, rstd, M, D, rowmask, mask_period, dx_in, dx_out,                            \
-        dgamma ? workspace : nullptr, m_live, dy_scale, (TT*)nullptr, (const float*)nullptr, 1.f, (float*)nullptr))
+        parts, m_live, dy_scale, (TT*)nullptr, (const float*)nullptr, 1.f, (float*)nullptr))
         switch ((D + 255) >> 8) {
             case 1: LN_BWD_RAGGED(1); break;
             case 2: LN_BWD_RAGGED(2); break;
@@ -880,63 +880,46 @@ int layernorm_bwd_impl(const void* dy, int dy_bf16, float dy_scale, const float*
     }
 #undef LN_BWD_LAUNCH
     EDITOR_LAUNCH_CHECK();
-    if (nparts) {
-        if (dgamma && dbeta != dgamma + D) return (int)hipErrorInvalidValue;
-        *nparts = (int)blocks;
-        return 0;
-    }
-    if (cast_partials) {
-        hipLaunchKernelGGL(reduce_rows_kernel, dim3((D + 63) / 64), dim3(1024), 0, stream, cast_partials, (int)blocks, (long)D,
-                           cast_colsum, 0, cast_colsum_scale);
-        EDITOR_LAUNCH_CHECK();
-    }
-    if (dgamma) {
-        // workspace rows are [block][2][D] = P rows of 2D columns; dgamma and dbeta must be ONE (2,D) buffer
-        // (dbeta == dgamma + D) so the reduction writes both without extra copies
-        if (dbeta != dgamma + D) return (int)hipErrorInvalidValue;
-        hipLaunchKernelGGL(reduce_rows_kernel, dim3((2 * D + 63) / 64), dim3(1024), 0, stream, workspace, (int)blocks,
-                           (long)2 * D, dgamma, 0, 1.f);
-        EDITOR_LAUNCH_CHECK();
-    }
+    *nparts = (int)blocks;
     return 0;
 }
 }  // namespace
 
 extern "C" int editor_layernorm_bwd(const void* dy, int dy_bf16, float dy_scale, const float* x, const float* gamma, const float* mean,
-    const float* rstd, long M, int D, const uint8_t* rowmask, int mask_period, const float* dx_in, float* dx_out,
-    float* dgamma, float* dbeta, float* workspace, int ws_rows, const int* m_live, hipStream_t stream)
+    const float* rstd, long M, int D, const uint8_t* rowmask, int mask_period, const float* dx_in, float* dx_out, float* parts,
+    int ws_rows, const int* m_live, int* nparts, hipStream_t stream)
 {
-    return layernorm_bwd_impl(dy, dy_bf16, dy_scale, x, gamma, mean, rstd, M, D, rowmask, mask_period, dx_in, dx_out, dgamma, dbeta,
-                              workspace, ws_rows, m_live, nullptr, nullptr, 1.f, nullptr, 1.f, stream);
+    return layernorm_bwd_impl(dy, dy_bf16, dy_scale, x, gamma, mean, rstd, M, D, rowmask, mask_period, dx_in, dx_out, parts, ws_rows,
+                              m_live, nullptr, nullptr, 1.f, 0, nullptr, nullptr, nullptr, nparts, stream);
 }
 
+// dy_perm / dy_live - dy lives on the COMPACTED rows of this LayerNorm's branch (stochastic depth, editor_droppath_plan; NULL:
+// dense); cast_perm - the cast output goes to the compacted rows of the branch that consumes it (NULL: dense).
 extern "C" int editor_layernorm_bwd_cast(const void* dy, int dy_bf16, float dy_scale, const float* x, const float* gamma,
-    const float* mean, const float* rstd, long M, int D, const float* dx_in, float* dx_out, float* dgamma, float* dbeta,
-    float* workspace, int ws_rows, void* cast_out, const float* cast_rowscale, float cast_scale, float* cast_colsum,
-    float cast_colsum_scale, hipStream_t stream)
+    const float* mean, const float* rstd, long M, int D, const float* dx_in, float* dx_out, float* parts, int ws_rows,
+    void* cast_out, const float* cast_rowscale, float cast_scale, int want_colsum, const int* dy_perm, const int* dy_live,
+    const int* cast_perm, int* nparts, hipStream_t stream)
 {
     if (!cast_out) return (int)hipErrorInvalidValue;
-    return layernorm_bwd_impl(dy, dy_bf16, dy_scale, x, gamma, mean, rstd, M, D, nullptr, 0, dx_in, dx_out, dgamma, dbeta, workspace,
-                              ws_rows, nullptr, cast_out, cast_rowscale, cast_scale, cast_colsum, cast_colsum_scale, stream);
+    return layernorm_bwd_impl(dy, dy_bf16, dy_scale, x, gamma, mean, rstd, M, D, nullptr, 0, dx_in, dx_out, parts, ws_rows, nullptr,
+                              cast_out, cast_rowscale, cast_scale, want_colsum, dy_perm, dy_live, cast_perm, nparts, stream);
 }
 
-namespace {
-int colsum_impl(const void* dy, int dy_bf16, long M, int N, long ld, float* out, float* workspace, int ws_rows, float scale,
-                hipStream_t stream, int* nparts)
+extern "C" int editor_colsum(const void* dy, int dy_bf16, long M, int N, long ld, float* parts, int ws_rows, int* nparts,
+                             hipStream_t stream)
 {
-    if (N % 4 || ws_rows < 1) return (int)hipErrorInvalidValue;
+    if (N % 4 || ws_rows < 1 || !parts || !nparts) return (int)hipErrorInvalidValue;
     int rows_per = 64;                                   // 16 rows per wave-group pass x 4
     while ((M + rows_per - 1) / rows_per > ws_rows) rows_per *= 2;
     const int gy = (int)((M + rows_per - 1) / rows_per);
     DISPATCH_T(dy_bf16, hipLaunchKernelGGL(colsum_kernel<TT>, dim3((N / 4 + 63) / 64, gy), dim3(256), 0, stream,
-               (const TT*)dy, M, N, ld, rows_per, workspace));
+               (const TT*)dy, M, N, ld, rows_per, parts));
     EDITOR_LAUNCH_CHECK();
-    if (nparts) { *nparts = gy; return 0; }
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3((N + 63) / 64), dim3(1024), 0, stream, workspace, gy, (long)N, out, 0, scale);
-    EDITOR_LAUNCH_CHECK();
+    *nparts = gy;
     return 0;
 }
 
+namespace {
 // Up to eight fixed-order folds out_j[c] = scale_j * sum_p partials_j[p][c] as ONE launch (blockIdx.y = job): a transformer
 // block's backward leaves six sets of partial rows (two LayerNorms' dgamma / dbeta, three bias gradients, one column sum from a
 // dgrad epilogue) whose totals nothing needs before the block ends - one launch per block instead of six (round 4: 95 -> 31
@@ -973,53 +956,6 @@ __global__ __launch_bounds__(1024) void reduce_rows_multi_kernel(ReduceJobs j)
     }
 }
 }  // namespace
-
-extern "C" int editor_colsum(const void* dy, int dy_bf16, long M, int N, long ld, float* out, float* workspace,
-                             int ws_rows, float scale, hipStream_t stream)
-{
-    return colsum_impl(dy, dy_bf16, M, N, ld, out, workspace, ws_rows, scale, stream, nullptr);
-}
-
-extern "C" int editor_colsum_parts(const void* dy, int dy_bf16, long M, int N, long ld, float* workspace, int ws_rows, int* nparts,
-                                   hipStream_t stream)
-{
-    if (!nparts) return (int)hipErrorInvalidValue;
-    return colsum_impl(dy, dy_bf16, M, N, ld, nullptr, workspace, ws_rows, 1.f, stream, nparts);
-}
-
-extern "C" int editor_layernorm_bwd_parts(const void* dy, int dy_bf16, float dy_scale, const float* x, const float* gamma,
-    const float* mean, const float* rstd, long M, int D, const uint8_t* rowmask, int mask_period, const float* dx_in, float* dx_out,
-    float* workspace, int ws_rows, const int* m_live, int* nparts, hipStream_t stream)
-{
-    if (!nparts || !workspace) return (int)hipErrorInvalidValue;
-    // (dgamma / dbeta: any non-NULL pair tells the kernel to write its partial rows; the totals are the caller's to fold)
-    return layernorm_bwd_impl(dy, dy_bf16, dy_scale, x, gamma, mean, rstd, M, D, rowmask, mask_period, dx_in, dx_out, workspace,
-                              workspace + D, workspace, ws_rows, m_live, nullptr, nullptr, 1.f, nullptr, 1.f, stream, nparts);
-}
-
-extern "C" int editor_layernorm_bwd_cast_parts(const void* dy, int dy_bf16, float dy_scale, const float* x, const float* gamma,
-    const float* mean, const float* rstd, long M, int D, const float* dx_in, float* dx_out, float* workspace, int ws_rows,
-    void* cast_out, const float* cast_rowscale, float cast_scale, int want_colsum, int* nparts, hipStream_t stream)
-{
-    if (!cast_out || !nparts || !workspace) return (int)hipErrorInvalidValue;
-    return layernorm_bwd_impl(dy, dy_bf16, dy_scale, x, gamma, mean, rstd, M, D, nullptr, 0, dx_in, dx_out, workspace, workspace + D,
-                              workspace, ws_rows, nullptr, cast_out, cast_rowscale, cast_scale, want_colsum ? workspace : nullptr,
-                              1.f, stream, nparts);
-}
-
-// editor_layernorm_bwd_cast_parts on COMPACTED rows (stochastic depth, editor_droppath_plan): dy_perm / dy_live - dy lives on the
-// compacted rows of this LayerNorm's branch (NULL: dense); cast_perm - the cast output goes to the compacted rows of the branch
-// that consumes it (NULL: dense).
-extern "C" int editor_layernorm_bwd_cast_perm_parts(const void* dy, int dy_bf16, float dy_scale, const float* x, const float* gamma,
-    const float* mean, const float* rstd, long M, int D, const float* dx_in, float* dx_out, float* workspace, int ws_rows,
-    void* cast_out, const float* cast_rowscale, float cast_scale, int want_colsum, const int* dy_perm, const int* dy_live,
-    const int* cast_perm, int* nparts, hipStream_t stream)
-{
-    if (!cast_out || !nparts || !workspace || (!dy_perm && !cast_perm)) return (int)hipErrorInvalidValue;
-    return layernorm_bwd_impl(dy, dy_bf16, dy_scale, x, gamma, mean, rstd, M, D, nullptr, 0, dx_in, dx_out, workspace, workspace + D,
-                              workspace, ws_rows, nullptr, cast_out, cast_rowscale, cast_scale, want_colsum ? workspace : nullptr,
-                              1.f, stream, nparts, dy_perm, dy_live, cast_perm);
-}
 
 extern "C" int editor_layernorm_fwd_perm(const float* x, const float* gamma, const float* beta, float eps, long M, int D, void* y,
     int y_bf16, float* mean, float* rstd, const int* perm, const float* rowscale, float* copy_out, hipStream_t stream)
@@ -1125,46 +1061,16 @@ extern "C" int editor_cast_rows(const float* in, const float* rowscale, long M, 
     return 0;
 }
 
-extern "C" int editor_cast_rows_colsum_perm_parts(const float* in, const float* rowscale, long M, int D, void* out, int out_bf16,
-                                                  float* workspace, int ws_rows, float scale, const int* perm, int* nparts,
-                                                  hipStream_t stream)
+extern "C" int editor_cast_rows_colsum(const float* in, const float* rowscale, long M, int D, void* out, int out_bf16, float* parts,
+                                       int ws_rows, float scale, const int* perm, int* nparts, hipStream_t stream)
 {
-    if ((D & 255) || D > 256 * kMaxV || ws_rows < 1 || !nparts || !workspace || !perm) return (int)hipErrorInvalidValue;
+    if ((D & 255) || D > 256 * kMaxV || ws_rows < 1 || !nparts || !parts) return (int)hipErrorInvalidValue;
     long blocks = (M + 3) / 4;
     if (blocks > ws_rows) blocks = ws_rows;
     DISPATCH_T(out_bf16, hipLaunchKernelGGL(cast_rows_colsum_kernel<TT>, dim3((unsigned)blocks), dim3(256), 0, stream,
-               in, rowscale, M, D, (TT*)out, workspace, scale, perm));
+               in, rowscale, M, D, (TT*)out, parts, scale, perm));
     EDITOR_LAUNCH_CHECK();
     *nparts = (int)blocks;
-    return 0;
-}
-
-extern "C" int editor_cast_rows_colsum_parts(const float* in, const float* rowscale, long M, int D, void* out, int out_bf16,
-                                             float* workspace, int ws_rows, float scale, int* nparts, hipStream_t stream)
-{
-    if ((D & 255) || D > 256 * kMaxV || ws_rows < 1 || !nparts || !workspace) return (int)hipErrorInvalidValue;
-    long blocks = (M + 3) / 4;
-    if (blocks > ws_rows) blocks = ws_rows;
-    DISPATCH_T(out_bf16, hipLaunchKernelGGL(cast_rows_colsum_kernel<TT>, dim3((unsigned)blocks), dim3(256), 0, stream,
-               in, rowscale, M, D, (TT*)out, workspace, scale));
-    EDITOR_LAUNCH_CHECK();
-    *nparts = (int)blocks;
-    return 0;
-}
-
-extern "C" int editor_cast_rows_colsum(const float* in, const float* rowscale, long M, int D, void* out, int out_bf16,
-                                       float* colsum, float* workspace, int ws_rows, float scale, float colsum_scale,
-                                       hipStream_t stream)
-{
-    if ((D & 255) || D > 256 * kMaxV || ws_rows < 1 || !colsum || !workspace) return (int)hipErrorInvalidValue;
-    long blocks = (M + 3) / 4;
-    if (blocks > ws_rows) blocks = ws_rows;
-    DISPATCH_T(out_bf16, hipLaunchKernelGGL(cast_rows_colsum_kernel<TT>, dim3((unsigned)blocks), dim3(256), 0, stream,
-               in, rowscale, M, D, (TT*)out, workspace, scale));
-    EDITOR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3((D + 63) / 64), dim3(1024), 0, stream, workspace, (int)blocks, (long)D, colsum,
-                       0, colsum_scale);
-    EDITOR_LAUNCH_CHECK();
     return 0;
 }
 

@@ -130,7 +130,7 @@ _ARENA = {}
 class ReduceQueue:
     """Deferred second stages of the deterministic two-stage reductions of ONE transformer block's backward (LayerNorm dgamma /
     dbeta, bias gradients, the dgrad epilogue's column sums): the producers leave their partial rows in regions of a per-stream
-    arena (the `_parts` entry points) and `flush()` folds up to eight sets with one editor_reduce_rows_multi launch - nothing needs
+    arena and `flush()` folds up to eight sets with one editor_reduce_rows_multi launch - nothing needs
     the totals before the block ends.  Round 4: 95 -> ~31 reduce launches per step, same bits (same summation order)."""
     ARENA_FLOATS = 16 << 20           # 64 MiB; one block's six sets are ~31 MB at D = 768, ~42 MB at D = 1024
 
@@ -175,13 +175,33 @@ class ReduceQueue:
             self.off = self.base
 
 
+def _parts_buf(rq, device, nfloats, fresh=False):
+    """Scratch for a two-stage producer's partial rows -> (buf, queued): the queue's region when there is a queue and the request
+    fits it, else the stream's workspace (fresh: a new tensor - for callers whose launch already uses the workspace)."""
+    buf = rq.region(nfloats) if rq is not None else None
+    if buf is not None:
+        return buf, True
+    return (torch.empty(int(nfloats), dtype=torch.float32, device=device) if fresh else workspace(device, nfloats)), False
+
+
+def _fold(rq, queued, buf, nparts, ncol, out, scale=1.0):
+    """Second stage of a two-stage reduction, out[c] = scale * sum_p buf[p][c]: at the queue's flush, or on the spot."""
+    if queued:
+        rq.add(buf, nparts, ncol, out, scale)
+    else:
+        call("editor_reduce_rows", buf, int(nparts), int(ncol), out, 0, float(scale))
+
+
 _DT_CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 HALF_DTYPES = (torch.bfloat16, torch.float16)
 
 
-def _is_bf16(t):
+def _dtype_code(t):
     """dtype code of the C ABI (include/editor_hip.h): 0 = fp32, 1 = bf16, 2 = f16."""
     return _DT_CODE[t.dtype]
+
+
+_is_bf16 = _dtype_code            # (earlier name)
 
 
 def _h16(t, name):
@@ -207,7 +227,7 @@ def layernorm_fwd(x2d, gamma, beta, eps, out_dtype, rowmask=None, mask_period=0,
     y = torch.empty(m, d, dtype=out_dtype, device=x2d.device)
     mean = torch.empty(m, dtype=torch.float32, device=x2d.device) if want_stats else None
     rstd = torch.empty(m, dtype=torch.float32, device=x2d.device) if want_stats else None
-    call("editor_layernorm_fwd", x2d, gamma, beta, float(eps), m, d, rowmask, int(mask_period), y, _is_bf16(y), mean, rstd,
+    call("editor_layernorm_fwd", x2d, gamma, beta, float(eps), m, d, rowmask, int(mask_period), y, _dtype_code(y), mean, rstd,
          m_live)
     return y, mean, rstd
 
@@ -219,7 +239,7 @@ def layernorm_fwd_perm(x2d, gamma, beta, eps, out_dtype, perm, rowscale, copy_ou
     y = torch.empty(m, d, dtype=out_dtype, device=x2d.device)
     mean = torch.empty(m, dtype=torch.float32, device=x2d.device)
     rstd = torch.empty(m, dtype=torch.float32, device=x2d.device)
-    call("editor_layernorm_fwd_perm", x2d, gamma, beta, float(eps), m, d, y, _is_bf16(y), mean, rstd, perm, rowscale, copy_out)
+    call("editor_layernorm_fwd_perm", x2d, gamma, beta, float(eps), m, d, y, _dtype_code(y), mean, rstd, perm, rowscale, copy_out)
     return y, mean, rstd
 
 
@@ -231,7 +251,7 @@ def resid_add_layernorm_fwd(x2d, branch, rowscale, gamma, beta, eps):
     y = torch.empty(m, d, dtype=branch.dtype, device=x2d.device)
     mean = torch.empty(m, dtype=torch.float32, device=x2d.device)
     rstd = torch.empty(m, dtype=torch.float32, device=x2d.device)
-    call("editor_resid_add_layernorm_fwd", x2d, branch, _is_bf16(branch), rowscale, gamma, beta, float(eps), m, d, x_out, y, mean, rstd)
+    call("editor_resid_add_layernorm_fwd", x2d, branch, _dtype_code(branch), rowscale, gamma, beta, float(eps), m, d, x_out, y, mean, rstd)
     return x_out, y, mean, rstd
 
 
@@ -247,16 +267,12 @@ def layernorm_bwd(dy, x2d, gamma, mean, rstd, rowmask=None, mask_period=0, dx_in
         dgb = torch.empty(2, d, dtype=torch.float32, device=x2d.device) if want_param_grads else None
     dg = dgb[0] if want_param_grads else None
     db = dgb[1] if want_param_grads else None
-    ws = rq.region(WS_ROWS * 2 * d) if (rq is not None and want_param_grads) else None
-    if ws is not None:
-        npart = ctypes.c_int(0)
-        call("editor_layernorm_bwd_parts", dy, _is_bf16(dy), float(dy_scale), x2d, gamma, mean, rstd, m, d, rowmask, int(mask_period),
-             dx_in, dx, ws, WS_ROWS, m_live, ctypes.byref(npart))
-        rq.add(ws, npart.value, 2 * d, dgb, 1.0)
-        return dx, dg, db
-    ws = workspace(x2d.device, WS_ROWS * 2 * d)
-    call("editor_layernorm_bwd", dy, _is_bf16(dy), float(dy_scale), x2d, gamma, mean, rstd, m, d, rowmask, int(mask_period), dx_in, dx,
-         dg, db, ws, WS_ROWS, m_live)
+    ws, queued = _parts_buf(rq, x2d.device, WS_ROWS * 2 * d) if want_param_grads else (None, False)
+    npart = ctypes.c_int(0)
+    call("editor_layernorm_bwd", dy, _dtype_code(dy), float(dy_scale), x2d, gamma, mean, rstd, m, d, rowmask, int(mask_period), dx_in, dx,
+         ws, WS_ROWS, m_live, ctypes.byref(npart))
+    if want_param_grads:
+        _fold(rq, queued, ws, npart.value, 2 * d, dgb)
     return dx, dg, db
 
 
@@ -267,39 +283,19 @@ def layernorm_bwd_cast(dy, x2d, gamma, mean, rstd, dx_in, rowscale, scale=1.0, d
     dy_perm / dy_live: dy sits on the compacted rows of a stochastic-depth plan (slots >= *dy_live: dropped rows, gradient zero);
     cast_perm: dx16 is written onto the compacted rows of the branch that consumes it (droppath_plan)."""
     m, d = x2d.shape
-    if dy_perm is not None or cast_perm is not None:
-        if rq is None:
-            raise RuntimeError("layernorm_bwd_cast on compacted rows: the deferred-reduction (parts) form only")
-        dx = torch.empty(m, d, dtype=torch.float32, device=x2d.device)
-        dgb = dgb_out if dgb_out is not None else torch.empty(2, d, dtype=torch.float32, device=x2d.device)
-        dx16 = torch.empty(m, d, dtype=dy.dtype, device=x2d.device)
-        cs = (cs_out if cs_out is not None else torch.empty(d, dtype=torch.float32, device=x2d.device)) if want_colsum else None
-        ws = rq.region(WS_ROWS * 3 * d)
-        npart = ctypes.c_int(0)
-        call("editor_layernorm_bwd_cast_perm_parts", dy, _is_bf16(dy), float(dy_scale), x2d, gamma, mean, rstd, m, d, dx_in, dx, ws,
-             WS_ROWS, dx16, rowscale, float(scale), 1 if want_colsum else 0, dy_perm, dy_live, cast_perm, ctypes.byref(npart))
-        rq.add(ws, npart.value, 2 * d, dgb, 1.0)
-        if want_colsum:
-            rq.add(ws[WS_ROWS * 2 * d:], npart.value, d, cs, 1.0 / float(scale))
-        return dx, dgb[0], dgb[1], dx16, cs
     dx = torch.empty(m, d, dtype=torch.float32, device=x2d.device)
     dgb = dgb_out if dgb_out is not None else torch.empty(2, d, dtype=torch.float32, device=x2d.device)
     dx16 = torch.empty(m, d, dtype=dy.dtype, device=x2d.device)
     cs = None
     if want_colsum:
         cs = cs_out if cs_out is not None else torch.empty(d, dtype=torch.float32, device=x2d.device)
-    ws = rq.region(WS_ROWS * 3 * d) if rq is not None else None
-    if ws is not None:
-        npart = ctypes.c_int(0)
-        call("editor_layernorm_bwd_cast_parts", dy, _is_bf16(dy), float(dy_scale), x2d, gamma, mean, rstd, m, d, dx_in, dx, ws, WS_ROWS,
-             dx16, rowscale, float(scale), 1 if want_colsum else 0, ctypes.byref(npart))
-        rq.add(ws, npart.value, 2 * d, dgb, 1.0)
-        if want_colsum:
-            rq.add(ws[WS_ROWS * 2 * d:], npart.value, d, cs, 1.0 / float(scale))
-        return dx, dgb[0], dgb[1], dx16, cs
-    ws = workspace(x2d.device, WS_ROWS * 3 * d)
-    call("editor_layernorm_bwd_cast", dy, _is_bf16(dy), float(dy_scale), x2d, gamma, mean, rstd, m, d, dx_in, dx, dgb[0], dgb[1],
-         ws, WS_ROWS, dx16, rowscale, float(scale), cs, 1.0 / float(scale))
+    ws, queued = _parts_buf(rq, x2d.device, WS_ROWS * 3 * d)
+    npart = ctypes.c_int(0)
+    call("editor_layernorm_bwd_cast", dy, _dtype_code(dy), float(dy_scale), x2d, gamma, mean, rstd, m, d, dx_in, dx, ws, WS_ROWS,
+         dx16, rowscale, float(scale), 1 if want_colsum else 0, dy_perm, dy_live, cast_perm, ctypes.byref(npart))
+    _fold(rq, queued, ws, npart.value, 2 * d, dgb)
+    if want_colsum:
+        _fold(rq, queued, ws[WS_ROWS * 2 * d:], npart.value, d, cs, 1.0 / float(scale))
     return dx, dgb[0], dgb[1], dx16, cs
 
 
@@ -307,26 +303,22 @@ def colsum(dy, out=None, scale=1.0, rq=None):
     m, n = dy.shape
     if out is None:
         out = torch.empty(n, dtype=torch.float32, device=dy.device)
-    ws = rq.region(WS_ROWS * n) if rq is not None else None
-    if ws is not None:
-        npart = ctypes.c_int(0)
-        call("editor_colsum_parts", dy, _is_bf16(dy), m, n, n, ws, WS_ROWS, ctypes.byref(npart))
-        rq.add(ws, npart.value, n, out, float(scale))
-        return out
-    ws = workspace(dy.device, WS_ROWS * n)
-    call("editor_colsum", dy, _is_bf16(dy), m, n, n, out, ws, WS_ROWS, float(scale))
+    ws, queued = _parts_buf(rq, dy.device, WS_ROWS * n)
+    npart = ctypes.c_int(0)
+    call("editor_colsum", dy, _dtype_code(dy), m, n, n, ws, WS_ROWS, ctypes.byref(npart))
+    _fold(rq, queued, ws, npart.value, n, out, scale)
     return out
 
 
 def gelu_fwd(a):
     g = torch.empty_like(a)
-    call("editor_gelu_fwd", a, g, a.numel(), _is_bf16(a))
+    call("editor_gelu_fwd", a, g, a.numel(), _dtype_code(a))
     return g
 
 
 def gelu_bwd(a, dg):
     da = torch.empty_like(a)
-    call("editor_gelu_bwd", a, dg, da, a.numel(), _is_bf16(a))
+    call("editor_gelu_bwd", a, dg, da, a.numel(), _dtype_code(a))
     return da
 
 
@@ -351,7 +343,7 @@ def cast_rows(x2d, rowscale, dtype, m_live=None, scale=1.0):
     """x * rowscale[:, None] * scale cast to `dtype` (one pass)."""
     m, d = x2d.shape
     out = torch.empty(m, d, dtype=dtype, device=x2d.device)
-    call("editor_cast_rows", x2d, rowscale, m, d, out, _is_bf16(out), m_live, float(scale))
+    call("editor_cast_rows", x2d, rowscale, m, d, out, _dtype_code(out), m_live, float(scale))
     return out
 
 
@@ -361,22 +353,10 @@ def cast_rows_colsum(x2d, rowscale, dtype, scale=1.0, cs_out=None, rq=None, perm
     m, d = x2d.shape
     out = torch.empty(m, d, dtype=dtype, device=x2d.device)
     cs = cs_out if cs_out is not None else torch.empty(d, dtype=torch.float32, device=x2d.device)
-    ws = rq.region(WS_ROWS * d) if rq is not None else None
-    if perm is not None:
-        if ws is None:
-            raise RuntimeError("cast_rows_colsum onto compacted rows: the deferred-reduction (parts) form only")
-        npart = ctypes.c_int(0)
-        call("editor_cast_rows_colsum_perm_parts", x2d, rowscale, m, d, out, _is_bf16(out), ws, WS_ROWS, float(scale), perm,
-             ctypes.byref(npart))
-        rq.add(ws, npart.value, d, cs, 1.0 / float(scale))
-        return out, cs
-    if ws is not None:
-        npart = ctypes.c_int(0)
-        call("editor_cast_rows_colsum_parts", x2d, rowscale, m, d, out, _is_bf16(out), ws, WS_ROWS, float(scale), ctypes.byref(npart))
-        rq.add(ws, npart.value, d, cs, 1.0 / float(scale))
-        return out, cs
-    ws = workspace(x2d.device, WS_ROWS * d)
-    call("editor_cast_rows_colsum", x2d, rowscale, m, d, out, _is_bf16(out), cs, ws, WS_ROWS, float(scale), 1.0 / float(scale))
+    ws, queued = _parts_buf(rq, x2d.device, WS_ROWS * d)
+    npart = ctypes.c_int(0)
+    call("editor_cast_rows_colsum", x2d, rowscale, m, d, out, _dtype_code(out), ws, WS_ROWS, float(scale), perm, ctypes.byref(npart))
+    _fold(rq, queued, ws, npart.value, d, cs, 1.0 / float(scale))
     return out, cs
 
 
@@ -390,7 +370,7 @@ def im2col16(img, dtype):
     for i, im in enumerate(imgs):
         if tuple(im.shape) != (b, c, h, w):
             raise ValueError("im2col16: modality tensors of different shapes")
-        call("editor_im2col16", im, b, c, h, w, _ptr(out, i * rows * c * 256), _is_bf16(out))
+        call("editor_im2col16", im, b, c, h, w, _ptr(out, i * rows * c * 256), _dtype_code(out))
     return out
 
 
@@ -407,13 +387,13 @@ def im2col_patch(img, dtype, stride):
     for i, im in enumerate(imgs):
         if tuple(im.shape) != (b, c, h, w):
             raise ValueError("im2col_patch: modality tensors of different shapes")
-        call("editor_im2col_patch", im, b, c, h, w, int(sy), int(sx), _ptr(out, i * rows * c * 256), _is_bf16(out))
+        call("editor_im2col_patch", im, b, c, h, w, int(sy), int(sx), _ptr(out, i * rows * c * 256), _dtype_code(out))
     return out
 
 
 def embed_assemble(patch, cls, pos, sie, cam, coef, btot, t, d):
     x = torch.empty(btot, t, d, dtype=torch.float32, device=patch.device)
-    call("editor_embed_assemble", patch, _is_bf16(patch), cls, pos, sie, cam, 0 if cam is None else cam.numel(),
+    call("editor_embed_assemble", patch, _dtype_code(patch), cls, pos, sie, cam, 0 if cam is None else cam.numel(),
          float(coef), btot, t, d, x)
     return x
 
@@ -425,7 +405,7 @@ def embed_assemble_bwd(dx, cam, ncam, coef, dtype, scale=1.0):
     dsie = torch.empty(ncam, d, dtype=torch.float32, device=dx.device) if ncam else None
     ws = workspace(dx.device, max(btot * d, 8 * t * d))          # EDITOR_EMBED_POS_SPLITS partial rows / per-sample row sums
     call("editor_embed_assemble_bwd", dx, cam, 0 if cam is None else cam.numel(), int(ncam), float(coef), btot, t, d,
-         dpatch, _is_bf16(dpatch), float(scale), dpos, dsie, ws)
+         dpatch, _dtype_code(dpatch), float(scale), dpos, dsie, ws)
     return dpatch, dpos, dsie
 
 
@@ -577,17 +557,11 @@ def gemm(a, b, c, m, n, k, lda, ldb, ldc, trans_a=0, trans_b=0, alpha=1.0, beta=
             # per-tile-row partials from the GEMM epilogue, folded in a fixed order
             assert gemm_colsum_ok(m, n, k, c.dtype, trans_a, splitk, m_live, live_dense) and ldc == n and rowmap is None
             tiles_m = (m + th - 1) // th
-            part = rq.region(tiles_m * n) if rq is not None else None
-            deferred = part is not None
-            if not deferred:
-                part = workspace(a.device, tiles_m * n)
+            part, queued = _parts_buf(rq, a.device, tiles_m * n)
             call(entry, _ptr(a, a_off), _ptr(b, b_off), _ptr(c, c_off), 0, m, n, k, lda, ldb, ldc,
                  int(trans_a), int(trans_b), float(alpha), float(beta), bias, rowscale, 1, int(epilogue) | EPI_COLSUM, aux,
                  n, part, m_live)
-            if deferred:
-                rq.add(part, tiles_m, n, colsum, float(colsum_scale))
-            else:
-                call("editor_reduce_rows", part, tiles_m, n, colsum, 0, float(colsum_scale))
+            _fold(rq, queued, part, tiles_m, n, colsum, colsum_scale)
             return
         if rowmap is not None:
             # compacted rows scattered back by the fp32 residual epilogue (stochastic-depth skipping: editor_gemm_h16_rows)
@@ -765,7 +739,6 @@ def gemm_group_ok(reqs):
 
 def gemm_group(reqs):
     """The requests of gemm_group_ok as one launch (editor_gemm_group): bit-identical to the separate ops.gemm calls."""
-    import ctypes
     cnt = len(reqs)
     a0, kw0 = reqs[0]
     a, b, c, m, n, k = a0[:6]
@@ -781,7 +754,6 @@ def gemm_wgrad_group(jobs, m, alpha=1.0, m_live=None):
     """jobs: list of (dy (m, n_i), x (m, k_i), dw (n_i, k_i) fp32[, live_i]) of ONE block -> one launch (editor_gemm_wgrad_group).
     live_i (optional 4th entry): device scalar, live token rows of THAT problem (rows beyond are zero) - a block whose MLP branch
     ran on stochastic-depth-compacted rows next to its dense attention branch (editor_gemm_wgrad_group_live)."""
-    import ctypes
     cnt = len(jobs)
     lives = [j[3] if len(j) > 3 else None for j in jobs]
     jobs = [j[:3] for j in jobs]
@@ -835,23 +807,15 @@ def gemm_wgrad_group_ln(jobs, m, alpha, dy, x2d, gamma, mean, rstd, dx_in, rowsc
     cs = None
     if want_colsum:
         cs = cs_out if cs_out is not None else torch.empty(d, dtype=torch.float32, device=dev)
-    parts = rq.region(nmem * 3 * d) if rq is not None else None
-    queued = parts is not None
-    if not queued:
-        parts = torch.empty(nmem * 3 * d, dtype=torch.float32, device=dev)
+    parts, queued = _parts_buf(rq, dev, nmem * 3 * d, fresh=True)
     cparts = parts[nmem * 2 * d:]
     call("editor_gemm_wgrad_group_ln", dt, cnt, arr([j[0] for j in jobs]), arr([j[1] for j in jobs]), arr([j[2] for j in jobs]),
          ia(ns), ia(ks), m, float(alpha), sk, ws,
          dy, float(dy_scale), x2d, gamma, mean, rstd, rows, d, dx_in, dx, parts, dx16, rowscale, float(scale),
          cparts if want_colsum else None, nmem)
-    if queued:
-        rq.add(parts, nmem, 2 * d, dgb, 1.0)
-        if want_colsum:
-            rq.add(cparts, nmem, d, cs, 1.0 / float(scale))
-    else:
-        call("editor_reduce_rows", parts, nmem, 2 * d, dgb, 0, 1.0)
-        if want_colsum:
-            call("editor_reduce_rows", cparts, nmem, d, cs, 0, 1.0 / float(scale))
+    _fold(rq, queued, parts, nmem, 2 * d, dgb)
+    if want_colsum:
+        _fold(rq, queued, cparts, nmem, d, cs, 1.0 / float(scale))
     return dx, dgb[0], dgb[1], dx16, cs
 
 
@@ -929,15 +893,9 @@ def attention_bwd(qkv, dout, b, t, heads, hd, mask=None, saved=None, out=None, c
             call(_h16(qkv, "attention_bwd"), qkv, dout, out, saved, b, t, heads, hd, scale, mask, dqkv, ws, cu, rows)
         else:
             ncol = qkv.shape[1]
-            parts = rq.region(b * ncol) if rq is not None else None
-            queued = parts is not None
-            if not queued:
-                parts = torch.empty(b * ncol, dtype=torch.float32, device=qkv.device)
+            parts, queued = _parts_buf(rq, qkv.device, b * ncol, fresh=True)
             call(_h16(qkv, "attention_bwd_colsum"), qkv, dout, out, saved, b, t, heads, hd, scale, mask, dqkv, ws, cu, rows, parts)
-            if queued:
-                rq.add(parts, b, ncol, colsum, float(colsum_scale))
-            else:
-                call("editor_reduce_rows", parts, b, ncol, colsum, 0, float(colsum_scale))
+            _fold(rq, queued, parts, b, ncol, colsum, colsum_scale)
     return dqkv
 
 

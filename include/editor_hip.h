@@ -113,47 +113,37 @@ int editor_layernorm_fwd(const float* x, const float* gamma, const float* beta, 
 int editor_resid_add_layernorm_fwd(const float* x, const void* branch, int b16, const float* rowscale, const float* gamma,
                                    const float* beta, float eps, long M, int D, float* x_out, void* y, float* mean,
                                    float* rstd, editor_stream_t stream);
-/* backward: dx_out = (dx_in ? dx_in : 0) + dLN/dx ; dgamma/dbeta: ONE (2,D) fp32 buffer (dbeta == dgamma + D; NULL to
- * skip).  workspace: ws_rows*2*D floats. */
+/* Two-stage reductions: the producers below leave per-workgroup PARTIAL ROWS in the caller's fp32 scratch (`parts`) and report
+ * their count P in *nparts (host); the caller folds them - editor_reduce_rows, or several sets with ONE editor_reduce_rows_multi
+ * launch (a transformer block's backward: six sets, whose totals nothing needs before the block ends).  Both folds sum in the same
+ * fixed order.  Layouts: layernorm: [P][2][D] (dgamma | dbeta rows) at parts, and - cast form with want_colsum - the cast output's
+ * column sums [P][D] at parts + ws_rows*2*D; colsum / cast_rows_colsum: [P][N] / [P][D] at parts. */
+/* backward: dx_out = (dx_in ? dx_in : 0) + dLN/dx.  parts: ws_rows*2*D floats, or NULL for no parameter gradients (*nparts is
+ * still set). */
 int editor_layernorm_bwd(const void* dy, int dy_bf16, float dy_scale /* dy is multiplied by it on load */,
                          const float* x, const float* gamma, const float* mean,
                          const float* rstd, long M, int D, const uint8_t* rowmask, int mask_period,
-                         const float* dx_in, float* dx_out, float* dgamma, float* dbeta, float* workspace,
-                         int ws_rows, const int* m_live, editor_stream_t stream);
-/* The same (dense 16-bit dy, no row mask) with the consumer's cast fused in: also writes cast_out (dtype of dy) =
+                         const float* dx_in, float* dx_out, float* parts, int ws_rows, const int* m_live, int* nparts,
+                         editor_stream_t stream);
+/* The same (dense 16-bit dy, no row mask, D % 256 == 0) with the consumer's cast fused in: also writes cast_out (dtype of dy) =
  * round(dx_out * cast_rowscale[row] * cast_scale) - the drop-path-scaled, loss-scaled 16-bit gradient the previous linear
- * layer's backward takes (vit_pytorch.py:217-218 backward) - and, when cast_colsum != NULL, cast_colsum[n] =
- * cast_colsum_scale * sum_m cast_out[m,n] (that layer's bias gradient): what editor_cast_rows_colsum would compute in a
- * second pass over dx_out.  workspace: ws_rows*3*D floats. */
+ * layer's backward takes (vit_pytorch.py:217-218 backward) - and, with want_colsum, the partial rows of sum_m cast_out[m,n] (that
+ * layer's bias gradient): what editor_cast_rows_colsum would compute in a second pass over dx_out.  parts: ws_rows*3*D floats.
+ * Stochastic depth (editor_droppath_plan): dy on compacted rows (dy_perm: row -> slot, dy_live: device scalar - slots >= *dy_live
+ * are dropped rows whose gradient is zero and is not read; both NULL: dense dy) and / or the cast output written to the compacted
+ * rows of its consumer branch (cast_perm; NULL: dense). */
 int editor_layernorm_bwd_cast(const void* dy, int dy_bf16, float dy_scale, const float* x, const float* gamma,
                               const float* mean, const float* rstd, long M, int D, const float* dx_in, float* dx_out,
-                              float* dgamma, float* dbeta, float* workspace, int ws_rows, void* cast_out,
-                              const float* cast_rowscale, float cast_scale, float* cast_colsum, float cast_colsum_scale,
+                              float* parts, int ws_rows, void* cast_out, const float* cast_rowscale, float cast_scale,
+                              int want_colsum, const int* dy_perm, const int* dy_live, const int* cast_perm, int* nparts,
                               editor_stream_t stream);
-/* "_parts" forms (round 4): the same kernels WITHOUT their second-stage fold - the partial rows stay in the caller's workspace
- * and *nparts (host) receives their count P; the caller folds several such sets with ONE editor_reduce_rows_multi launch (a
- * transformer block's backward: six sets, whose totals nothing needs before the block ends).  Layouts: layernorm: [P][2][D]
- * (dgamma | dbeta rows) at workspace, and - cast form with want_colsum - the cast output's column sums [P][D] at
- * workspace + ws_rows*2*D; colsum / cast_rows_colsum: [P][N] / [P][D] at workspace. */
-int editor_layernorm_bwd_parts(const void* dy, int dy_bf16, float dy_scale, const float* x, const float* gamma,
-                               const float* mean, const float* rstd, long M, int D, const uint8_t* rowmask, int mask_period,
-                               const float* dx_in, float* dx_out, float* workspace, int ws_rows, const int* m_live,
-                               int* nparts, editor_stream_t stream);
-int editor_layernorm_bwd_cast_parts(const void* dy, int dy_bf16, float dy_scale, const float* x, const float* gamma,
-                                    const float* mean, const float* rstd, long M, int D, const float* dx_in, float* dx_out,
-                                    float* workspace, int ws_rows, void* cast_out, const float* cast_rowscale,
-                                    float cast_scale, int want_colsum, int* nparts, editor_stream_t stream);
-int editor_colsum_parts(const void* dy, int dy_bf16, long M, int N, long ld, float* workspace, int ws_rows, int* nparts,
-                        editor_stream_t stream);
-int editor_cast_rows_colsum_parts(const float* in, const float* rowscale, long M, int D, void* out, int out_bf16,
-                                  float* workspace, int ws_rows, float scale, int* nparts, editor_stream_t stream);
 /* count <= 8 folds out[j][c] = scale[j] * sum_{p < P[j]} partials[j][p * ncol[j] + c] in one launch; the five arrays are HOST
  * arrays of `count` entries (device pointers inside).  Same fixed summation order as editor_reduce_rows. */
 int editor_reduce_rows_multi(int count, const float* const* partials, const int* P, const long* ncol, float* const* out,
                              const float* scale, editor_stream_t stream);
-/* out[n] = scale * sum_m dy[m,n]  (bias gradients of every nn.Linear).  workspace: ws_rows*N floats. */
-int editor_colsum(const void* dy, int dy_bf16, long M, int N, long ld, float* out, float* workspace, int ws_rows,
-                  float scale, editor_stream_t stream);
+/* partial rows of sum_m dy[m,n]  (bias gradients of every nn.Linear).  parts: ws_rows*N floats. */
+int editor_colsum(const void* dy, int dy_bf16, long M, int N, long ld, float* parts, int ws_rows, int* nparts,
+                  editor_stream_t stream);
 int editor_reduce_rows(const float* partials, int P, long ncol, float* out, int accumulate, float scale,
                        editor_stream_t stream);
 /* nn.GELU() exact erf (vit_pytorch.py:130,141) and its derivative */
@@ -166,11 +156,11 @@ int editor_cast_f16_to_f32(const uint16_t* in, float* out, long n, editor_stream
  * per-sample drop-path factor keep/keep_prob of vit_pytorch.py:52-69 (and the f16 loss scale) folded in. */
 int editor_cast_rows(const float* in, const float* rowscale, long M, int D, void* out, int out_bf16,
                      const int* m_live, float scale, editor_stream_t stream);
-/* editor_cast_rows plus colsum[d] = sum_m out[m,d] (the rounded values): the bias gradient of the nn.Linear that `out`
- * feeds, without another pass over it.  D a multiple of 256; workspace: ws_rows*D floats. */
-int editor_cast_rows_colsum(const float* in, const float* rowscale, long M, int D, void* out, int out_bf16, float* colsum,
-                            float* workspace, int ws_rows, float scale, float colsum_scale /* applied to colsum only */,
-                            editor_stream_t stream);
+/* editor_cast_rows plus the partial rows of sum_m out[m,d] (the rounded values): the bias gradient of the nn.Linear that `out`
+ * feeds, without another pass over it.  D a multiple of 256; parts: ws_rows*D floats.  perm (NULL: dense): row r goes to row
+ * perm[r] of out (compacted consumer rows, editor_droppath_plan). */
+int editor_cast_rows_colsum(const float* in, const float* rowscale, long M, int D, void* out, int out_bf16, float* parts,
+                            int ws_rows, float scale, const int* perm, int* nparts, editor_stream_t stream);
 int editor_cast_bf16_to_f32(const uint16_t* in, float* out, long n, editor_stream_t stream);
 
 /* split-precision producers (COMPUTE_DTYPE 'f16x2'): the same kernels writing x as the half pair hi = half(x),
@@ -264,7 +254,7 @@ int editor_gemm_wgrad_group(int dtype, int count, const uint16_t* const* dy, con
 /* The same launch (dense rows: no m_live) with a MEMORY-BOUND ROLE riding in it (round 4, opt-in: cfg / EDITOR_WGRAD_LN=1): the first
  * `nmem` workgroups (8 .. 256, a multiple of 8) do the LayerNorm backward that is independent of, and adjacent to, the block's
  * weight gradients (Block.norm1, vit_pytorch.py:215-220 backward) WITH the 16-bit copy of its result for the block below - exactly
- * editor_layernorm_bwd_cast_parts' arithmetic per row (D = 768 or 1024): dx_out = dLN(ln_dy * ln_dy_scale) + dx_in, cast_out =
+ * editor_layernorm_bwd_cast's arithmetic per row (D = 768 or 1024): dx_out = dLN(ln_dy * ln_dy_scale) + dx_in, cast_out =
  * 16-bit(dx_out * cast_rowscale[row] * cast_scale); partial rows, ONE PER MEMORY WORKGROUP: partials [nmem][2][D] (dgamma, dbeta),
  * cast_partials [nmem][D] (column sums of the rounded copy; NULL to skip) - to be folded by editor_reduce_rows(_multi) with P = nmem.
  * On this runtime an HBM-bound and an MFMA-bound kernel do not overlap across queues; two roles of one launch do. */
@@ -582,18 +572,6 @@ int editor_droppath_plan(const float* scales, int L, long B, int T, int* perm, i
 int editor_layernorm_fwd_perm(const float* x, const float* gamma, const float* beta, float eps, long M, int D, void* y, int y_bf16,
                               float* mean, float* rstd, const int* perm, const float* rowscale, float* copy_out,
                               editor_stream_t stream);
-/* editor_layernorm_bwd_cast_parts with dy on compacted rows (dy_perm: row -> slot, dy_live: device scalar - slots >= *dy_live are
- * dropped rows whose gradient is zero and is not read; both NULL: dense dy) and / or the cast output written to the compacted rows
- * of its consumer branch (cast_perm; NULL: dense). */
-int editor_layernorm_bwd_cast_perm_parts(const void* dy, int dy_bf16, float dy_scale, const float* x, const float* gamma,
-                                         const float* mean, const float* rstd, long M, int D, const float* dx_in, float* dx_out,
-                                         float* workspace, int ws_rows, void* cast_out, const float* cast_rowscale,
-                                         float cast_scale, int want_colsum, const int* dy_perm, const int* dy_live,
-                                         const int* cast_perm, int* nparts, editor_stream_t stream);
-/* editor_cast_rows_colsum_parts writing row r to row perm[r] of out */
-int editor_cast_rows_colsum_perm_parts(const float* in, const float* rowscale, long M, int D, void* out, int out_bf16,
-                                       float* workspace, int ws_rows, float scale, const int* perm, int* nparts,
-                                       editor_stream_t stream);
 /* editor_gemm_bf16 / _f16 (dtype 1 / 2; A (M,K), B (N,K) k-major, fp32 C, EDITOR_EPI_RESIDUAL) on compacted rows: output row m is
  * scattered to row rowmap[m] of C, reading aux and rowscale there (rowmap = inv of editor_droppath_plan); m_live as editor_gemm_bf16.
  * Unwritten-row contract of the compacted MLP branch (m_live = the live prefix; rows [*m_live, M) of its operands are zero):

@@ -1,6 +1,6 @@
 """Stochastic-depth compaction (round 6): the MLP branch of a backbone block runs on the samples its drop-path draw kept
 (vit_pytorch.py:52-69,217-218: a dropped sample's branch is multiplied by 0 and gets no gradient through it).  The kernels
-that carry it - editor_droppath_plan, editor_layernorm_fwd_perm, editor_gemm_h16_rows, the *_perm_parts backward forms, the
+that carry it - editor_droppath_plan, editor_layernorm_fwd_perm, editor_gemm_h16_rows, the perm forms of the backward row kernels, the
 per-problem live counts of the grouped weight gradients - against their dense counterparts, then the whole training step
 with the skipping on against the step with it off: forward outputs and input gradients BIT-identical (a live row's
 arithmetic does not depend on where the row sits), weight gradients equal up to the fp32 summation order of the reduction

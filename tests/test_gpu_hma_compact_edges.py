@@ -303,7 +303,7 @@ def test_layernorm_and_cast_rows_with_m_live(name, b, pad, monkeypatch):
                 dx2, dg2, db2 = ops.layernorm_bwd(dy, x, gam, mean, rstd, mask, 0, dx_in=dx_in, m_live=lv, rq=rq)
                 rq.flush()
                 torch.cuda.synchronize()
-            for tag, dx_, dg_, db_ in (("bwd", dx, dg, db), ("bwd_parts", dx2, dg2, db2)):
+            for tag, dx_, dg_, db_ in (("bwd", dx, dg, db), ("bwd_queued", dx2, dg2, db2)):
                 w2 = what + (tag, dt)
                 _check(dx_[:live], dx_ref, 2e-5, m, w2)
                 _finite(dx_[live:r64], w2 + ("dx pad rows",))

@@ -18,6 +18,10 @@ PRESETS = {
     # BASELINE.json config 5 (synthetic extension, no dataset): 4 modalities, ViT-L/16, 512x256 input -> 512 patch tokens
     "SYNTH4L": dict(size=(512, 256), al=0, num_class=171, cams=4,
                     extra=dict(transformer_type="vit_large_patch16_224", num_modalities=4)),
+    # RGB + NIR vehicles (data/datasets/RGBNT300.py, make_model.py:260-360 forward_two_modalities): no configs/ entry in the
+    # reference, so the RGBNT100 geometry; the data set is not at hand: C=150, cams=8 chosen (RGBNT300.py:81-82 only bound
+    # pid <= 600, camid <= 8)
+    "RGBN300": dict(size=(128, 256), al=0, num_class=150, cams=8, extra=dict(num_modalities=2)),
 }
 MODALITY_KEYS = ("RGB", "NI", "TI", "M4")
 

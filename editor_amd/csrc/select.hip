@@ -172,6 +172,8 @@ __global__ __launch_bounds__(256) void freq_counts_kernel(
 // the inputs it does not cover (denormals, infinities: a wave-uniform, never-taken branch on image data).  ~1 600 instructions
 // per 16 pixels: 3.7x fewer per pixel, same arithmetic per element (same haar_fwd / haar_inv expressions, same summation
 // orders) - bit-identical counts (tests/test_gpu_select.py against the reference's goldens and against the kernel above).
+// Built for 2, 3 and 4 modalities.  Two (forward_two_modalities, RGB + NIR): the mean is an exact halving of (Ylx + Yly), summed in
+// that order as Frequency.py:76-79 does, so the rare-input branch never fires for it.
 template <int XM> __device__ __forceinline__ float lane_xor16(float v)
 {
     // value of lane (l ^ XM), XM < 16: inside a row of 16 lanes
@@ -371,7 +373,9 @@ static int freq_counts_stride_launch(const float* m0, const float* m1, const flo
     const dim3 grid((unsigned)((tiles + 3) / 4)), grid4((unsigned)((tiles + 15) / 16)), block(256);
     const bool al16 = ((reinterpret_cast<uintptr_t>(m0) | reinterpret_cast<uintptr_t>(m1) | reinterpret_cast<uintptr_t>(m2) |
                         reinterpret_cast<uintptr_t>(m3)) & 15) == 0;
-    if (nmod == 3 && C == 3 && al16)
+    if (nmod == 2 && C == 3 && al16)
+        hipLaunchKernelGGL((freq_counts4_kernel<2, 3, uint16_t>), grid4, block, 0, stream, m0, m1, m2, m3, B, H, W, plane);
+    else if (nmod == 3 && C == 3 && al16)
         hipLaunchKernelGGL((freq_counts4_kernel<3, 3, uint16_t>), grid4, block, 0, stream, m0, m1, m2, m3, B, H, W, plane);
     else if (nmod == 4 && C == 3 && al16)
         hipLaunchKernelGGL((freq_counts4_kernel<4, 3, uint16_t>), grid4, block, 0, stream, m0, m1, m2, m3, B, H, W, plane);
@@ -394,7 +398,9 @@ static int freq_counts_launch(const float* m0, const float* m1, const float* m2,
     const dim3 grid4((unsigned)((tiles + 15) / 16));            // 4 x 4 pixels per lane: four patches per wave, 16 per block
     const bool al16 = ((reinterpret_cast<uintptr_t>(m0) | reinterpret_cast<uintptr_t>(m1) | reinterpret_cast<uintptr_t>(m2) |
                         reinterpret_cast<uintptr_t>(m3)) & 15) == 0;
-    if (nmod == 3 && C == 3 && al16 && variant == 0)
+    if (nmod == 2 && C == 3 && al16 && variant == 0)
+        hipLaunchKernelGGL((freq_counts4_kernel<2, 3>), grid4, block, 0, stream, m0, m1, m2, m3, B, H, W, counts);
+    else if (nmod == 3 && C == 3 && al16 && variant == 0)
         hipLaunchKernelGGL((freq_counts4_kernel<3, 3>), grid4, block, 0, stream, m0, m1, m2, m3, B, H, W, counts);
     else if (nmod == 4 && C == 3 && al16 && variant == 0)
         hipLaunchKernelGGL((freq_counts4_kernel<4, 3>), grid4, block, 0, stream, m0, m1, m2, m3, B, H, W, counts);

@@ -503,8 +503,9 @@ class TransformerBlockFn(torch.autograd.Function):
         # computed: LayerNorm-2 writes the live samples' rows compacted, fc1 / fc2 and the whole MLP backward run on that prefix
         # (`live` rows, a device scalar: tiles beyond it exit), the fc2 epilogue scatters back.  Same bits for every live row.
         # (the split-precision modes: the MLP's forward on half pairs - or, F16X2H, as plain f16 - and an f16 backward either way)
-        plan = drop_plan if _plan_ok(torch.float16 if act_dtype in (F16X2, F16X2H) else act_dtype, m, d, fc1w.shape[0], cu, mask,
-                                     m_live, branch16, defer_out, pend_branch, rowscale_mlp) else None
+        plan_ok = _plan_ok(torch.float16 if act_dtype in (F16X2, F16X2H) else act_dtype, m, d, fc1w.shape[0], cu, mask,
+                           m_live, branch16, defer_out, pend_branch, rowscale_mlp)
+        plan = drop_plan if plan_ok else None
         ctx.plan = plan
         head_done = split_all = False
         if act_dtype in (F16X2, F16X2H):
@@ -612,8 +613,11 @@ class TransformerBlockFn(torch.autograd.Function):
                            epilogue=ops.EPI_RESIDUAL, aux=x1, m_live=live, live_dense=True, rowmap=plan[1])
         else:
             x2 = torch.empty_like(x2d)
+            # plan_ok without a plan (cfg.MODEL.DROP_SKIP off): the product takes the ping-pong kernel, as its compacted form must (the
+            # row scatter is that kernel's epilogue) - at few token rows (two modalities at B = 32: 8 256) the tile-count heuristic of
+            # ops.gemm would pick the 256x128 kernel, whose fp32 sums round differently, and the switch would change the forward's bits
             yield _GemmReq(g, w2, x2, m, d, hidden, hidden, hidden, d, 0, 0, bias=fc2b, rowscale=rowscale_mlp,
-                           epilogue=ops.EPI_RESIDUAL, aux=x1, m_live=m_live)
+                           epilogue=ops.EPI_RESIDUAL | (ops.EPI_FORCE_PP if plan_ok else 0), aux=x1, m_live=m_live)
         if light:
             h1 = h2 = g = None                      # recomputed by the backward (n1b / n2b / eps ride along)
         ctx.save_for_backward(x2d, mean1, rstd1, h1, qkv, ao, x1, mean2, rstd2, h2, a, g, n1w, n2w,

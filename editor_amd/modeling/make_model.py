@@ -14,6 +14,9 @@ MI355X-first differences in HOW (not WHAT) it computes:
     probabilities from its saved q / k and row log-sum-exps (no probability tensor at all), the f32 parity mode and the
     split-precision 'f16x2' mode read the (L,3B,h,T,T) softmax buffer their attention kernels materialise;
   * top-k tie order of torch's CPU kernel is reproduced on device (libstdc++ heap/introselect).
+
+cfg.MODEL.NUM_MODALITIES = 2 builds the model of the reference's forward_two_modalities (make_model.py:260-360; RGB + NIR sets such as
+RGBN300): every stage below is written over `self.modalities`, so the same code runs on two stacked modalities (2B samples).
 """
 import math
 import os
@@ -282,9 +285,10 @@ class EDITOR(nn.Module):
         self.FREQ_INDEX = FrequencyIndex(cfg.MODEL.FREQUENCY_KEEP, stride[0])
         self.hma_heads = getattr(cfg.MODEL, "HMA_HEADS", 12 if dim % 12 == 0 else 16)    # make_model.py:97
         nmod = int(getattr(cfg.MODEL, "NUM_MODALITIES", 3))
-        if nmod not in (3, 4):
-            raise NotImplementedError("EDITOR fuses 3 modalities (make_model.py:153-155); NUM_MODALITIES = 4 is the "
-                                      "synthetic extension of BASELINE config 5")
+        if nmod not in (2, 3, 4):
+            raise NotImplementedError("NUM_MODALITIES = %d: EDITOR is built for 2, 3 or 4 modalities - 3 is the reference's forward "
+                                      "(make_model.py:153-155), 2 its forward_two_modalities (make_model.py:260-360, RGB + NIR), 4 "
+                                      "the synthetic extension of BASELINE config 5" % nmod)
         self.modalities = _MODALITIES[:nmod]
         self.nmod = nmod
         self.FUSE_block = BlockMask(dim, num_classes, 4.0, 0.8, self.modalities)
@@ -566,6 +570,18 @@ class EDITOR(nn.Module):
         finally:
             fn.set_model_options(grad_enabled=True)
 
+    def forward_two_modalities(self, x, cam_label=None, label=None, view_label=None, cross_type=None, img_path=None, mode=1,
+                               writer=None, epoch=None):
+        """The reference's forward for RGB + NIR data sets such as RGBN300 (make_model.py:260-360): x['RGB'] and x['NI'] (a 'TI' entry
+        is ignored).  Train: (score, cls4t, ori_score, ori, loss) with AL, else (score, cls4t, RGB_cls_score, RGB_cls4tri,
+        NIR_cls_score, NIR_cls4tri, loss); eval: cls4t (B, 2*dim), selected by the model's own SFTS path.  The model must have been
+        built with cfg.MODEL.NUM_MODALITIES = 2: the reference sizes FUSE_HEAD / FUSE_BN / AL_* at construction as well (its comment
+        at make_model.py:276 asks for that change by hand)."""
+        if self.nmod != 2:
+            raise ValueError("forward_two_modalities needs a model built with cfg.MODEL.NUM_MODALITIES = 2: FUSE_HEAD / FUSE_BN / "
+                             "AL_HEAD / AL_BN are sized at construction (this one: %d modalities)" % self.nmod)
+        return self.forward(x, cam_label, label, view_label, img_path, mode, writer, epoch)
+
     def _forward(self, x, cam_label=None, label=None, view_label=None, img_path=None, mode=1, writer=None, epoch=None):
         mods = [x[m_[0]].contiguous() for m_ in self.modalities]             # make_model.py:153-155
         rgb = mods[0]
@@ -581,8 +597,8 @@ class EDITOR(nn.Module):
         side = fn._side_stream(rgb.device)
         side.wait_stream(cur)
         with torch.no_grad(), torch.cuda.stream(side):
-            mask_fre, _ = ops.frequency_mask(mods[0], mods[1], mods[2], self.FREQ_INDEX.keep, mods[3] if nmod > 3 else None,
-                                             self.FREQ_INDEX.stride)
+            mask_fre, _ = ops.frequency_mask(mods[0], mods[1], mods[2] if nmod > 2 else None, self.FREQ_INDEX.keep,
+                                             mods[3] if nmod > 3 else None, self.FREQ_INDEX.stride)
             fre_done = side.record_event()
         feats, probs = self._backbone(mods, cam_label)
         t = feats.shape[1]
@@ -609,7 +625,7 @@ class EDITOR(nn.Module):
         else:                      # dense-masked form, as the reference computes it (always used in f32 parity mode)
             fused, loss_ocfr = self._hma(feats_s, index, label)
             pooled, num = fn.PoolFn.apply(fused, nmod, t)
-        if training and writer is not None:
+        if training and writer is not None and nmod > 2:          # (forward_two_modalities logs no num_count, make_model.py:305-309)
             writer.add_scalar("num_count", num.mean(), epoch)                      # make_model.py:199-200
         pooled_m = pooled.unbind(0)              # (unbind's backward is one stack; per-index selects zero-fill and add)
         red = [fn.LinearFn.apply(pooled_m[i], getattr(self, m_[1] + "_REDUCE").weight, getattr(self, m_[1] + "_REDUCE").bias)

@@ -548,7 +548,7 @@ def gemm(a, b, c, m, n, k, lda, ldb, ldc, trans_a=0, trans_b=0, alpha=1.0, beta=
         if (SHORT_TILES and not trans_a and not trans_b and splitk == 1 and beta == 0.0 and (m_live is None or live_dense) and m >= 2048
                 and n >= 512 and n % 8 == 0 and ldc % 8 == 0 and k % 64 == 0 and not (int(epilogue) & 0xF000)):
             th, narrow = gemm_tile_plan(m, n)
-            if narrow and colsum is None and not (int(epilogue) & EPI_FORCE_PP):
+            if narrow and colsum is None and rowmap is None and not (int(epilogue) & EPI_FORCE_PP):     # (a row map needs the ping-pong kernel)
                 th, epilogue = 256, int(epilogue) | EPI_PIPE128
             elif th != 256:
                 epilogue = int(epilogue) | EPI_TILE_ROWS(th)

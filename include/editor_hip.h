@@ -60,8 +60,11 @@ typedef struct ihipStream_t* editor_stream_t;   /* == hipStream_t */
 
 /* Frequency.py:65-84 + :42-56 - 4-level Haar DWT of each modality (pytorch_wavelets AFB2D, lowlevel.py:336-347),
  * coefficient mean over modalities, inverse DWT (SFB2D, lowlevel.py:671-680), channel mean, count of >0 pixels
- * per 16x16 window.  rgb/nir/tir: (B,C,H,W) fp32 NCHW (tir may be NULL: two-modality form);
- * counts: (B, H/16*W/16) int32, patches row-major as PatchEmbed flattens them (vit_pytorch.py:457). */
+ * per 16x16 window.  rgb/nir/tir: (B,C,H,W) fp32 NCHW (tir may be NULL: the two-modality form, the mean
+ * (Ylx + Yly) / 2 of Frequency.py:76-79 - what EDITOR.forward_two_modalities runs);
+ * counts: (B, H/16*W/16) int32, patches row-major as PatchEmbed flattens them (vit_pytorch.py:457).
+ * C == 3 with every base pointer 16-byte aligned takes the tile kernel (freq_counts4_kernel, built for 2, 3 and 4
+ * modalities); any other channel count or alignment (4 bytes at least) the generic wave-per-patch kernel - same counts. */
 int editor_freq_counts_f32(const float* rgb, const float* nir, const float* tir, int B, int C, int H, int W,
                            int32_t* counts, editor_stream_t stream);
 
@@ -75,7 +78,8 @@ int editor_freq_counts_nmod_f32(const float* m0, const float* m1, const float* m
  * of every 16x16 window at origin (py*s, px*s), ny = (H-16)/s + 1 by nx = (W-16)/s + 1 windows, row-major.  Two launches: the
  * tile kernel writes one 16-bit "> 0" row mask per (sample, image row, tile column) into `plane` (B*H*(W/16) uint16, caller's
  * scratch; the reconstructed image itself never reaches memory), a popcount kernel sums the windows.  1 <= s <= 16 (s = 16
- * equals editor_freq_counts_f32); H, W multiples of 16.  counts: (B, ny*nx) int32. */
+ * equals editor_freq_counts_f32); H, W multiples of 16.  counts: (B, ny*nx) int32.  tir may be NULL / nmod = 2 .. 4 and the choice
+ * between the tile kernel and the generic one are as for the entry points above. */
 int editor_freq_counts_stride_f32(const float* rgb, const float* nir, const float* tir, int B, int C, int H, int W, int stride,
                                   uint16_t* plane, int32_t* counts, editor_stream_t stream);
 int editor_freq_counts_stride_nmod_f32(const float* m0, const float* m1, const float* m2, const float* m3, int nmod, int B,

@@ -106,7 +106,77 @@ __global__ void resize_v_kernel(const uint8_t* __restrict__ in, int B, int Hin, 
     }
 }
 
+
+// ---- ragged batch: every image its own input size, one output size (include/editor_hip.h: desc / off / taps) ----------
+// three channels of one output pixel: cnt taps w[] over src, src + stride, ...; Pillow's seed and clip
+__device__ __forceinline__ void tap_sum3(const uint8_t* __restrict__ src, long stride, const int* __restrict__ w, int cnt,
+                                         uint8_t* __restrict__ o)
+{
+    int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+    for (int k = 0; k < cnt; ++k) {
+        const int wk = w[k];
+        const uint8_t* s = src + (long)k * stride;
+        a0 += s[0] * wk; a1 += s[1] * wk; a2 += s[2] * wk;
+    }
+    o[0] = clip8(a0); o[1] = clip8(a1); o[2] = clip8(a2);
+}
+// in: packed (H_i, W_i, 3) images -> tmp: packed (H_i, Wout, 3); one thread per intermediate pixel
+__global__ void resize_h_ragged_kernel(const uint8_t* __restrict__ in, int B, int Wout, const int* __restrict__ desc,
+                                       const long* __restrict__ off, const int* __restrict__ taps, long n, uint8_t* __restrict__ tmp)
+{
+    const long* prefix = off + 2L * B;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+        const int i = ragged_find(prefix, B, e);
+        const long p = e - (i ? prefix[i - 1] : 0);
+        const int xx = (int)(p % Wout);
+        const long y = p / Wout;
+        const int* d = desc + (long)i * 8;
+        const int* bounds = taps + d[2];
+        const int x0 = bounds[2 * xx], cnt = bounds[2 * xx + 1];
+        tap_sum3(in + off[i] + (y * d[1] + x0) * 3, 3, bounds + 2 * Wout + (long)xx * d[3], cnt, tmp + off[B + i] + p * 3);
+    }
+}
+// tmp: packed (H_i, Wout, 3) -> out: dense (B, Hout, Wout, 3)
+__global__ void resize_v_ragged_kernel(const uint8_t* __restrict__ tmp, int B, int Hout, int Wout, const int* __restrict__ desc,
+                                       const long* __restrict__ off, const int* __restrict__ taps, uint8_t* __restrict__ out)
+{
+    const long n = (long)B * Hout * Wout;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(e % Wout);
+        const int yy = (int)((e / Wout) % Hout);
+        const int b = (int)(e / ((long)Wout * Hout));
+        const int* d = desc + (long)b * 8;
+        const int* bounds = taps + d[4];
+        const int y0 = bounds[2 * yy], cnt = bounds[2 * yy + 1];
+        tap_sum3(tmp + off[B + b] + ((long)y0 * Wout + x) * 3, (long)Wout * 3, bounds + 2 * Hout + (long)yy * d[5], cnt, out + e * 3);
+    }
+}
+
 }  // namespace
+
+extern "C" int editor_resize_u8_ragged(const uint8_t* in, int B, int Hout, int Wout, const int* desc_host, const long* off_host,
+                                       const int* desc, const long* off, const int* taps, long ntaps, uint8_t* tmp, uint8_t* out,
+                                       editor_stream_t stream)
+{
+    if (B <= 0 || Hout <= 0 || Wout <= 0 || !in || !desc_host || !off_host || !desc || !off || !taps || ntaps <= 0 || !tmp || !out)
+        return (int)hipErrorInvalidValue;
+    long rows = 0;
+    for (int i = 0; i < B; ++i) {                                    // the kernels trust the tables
+        const int* d = desc_host + (long)i * 8;
+        if (d[0] <= 0 || d[1] <= 0 || d[3] < 1 || d[5] < 1 || d[2] < 0 || d[4] < 0 ||
+            d[2] + (long)Wout * (2 + d[3]) > ntaps || d[4] + (long)Hout * (2 + d[5]) > ntaps)
+            return (int)hipErrorInvalidValue;
+        rows += d[0];
+        if (off_host[i] < 0 || off_host[B + i] < 0 || off_host[2L * B + i] != rows * Wout) return (int)hipErrorInvalidValue;
+    }
+    auto blocks = [](long n) { long b = (n + 255) / 256; return (unsigned)(b > 65536 ? 65536 : b); };
+    const long nh = rows * Wout;
+    resize_h_ragged_kernel<<<blocks(nh), 256, 0, (hipStream_t)stream>>>(in, B, Wout, desc, off, taps, nh, tmp);
+    EDITOR_LAUNCH_CHECK();
+    resize_v_ragged_kernel<<<blocks((long)B * Hout * Wout), 256, 0, (hipStream_t)stream>>>(tmp, B, Hout, Wout, desc, off, taps, out);
+    EDITOR_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int editor_resize_u8(const uint8_t* in, int B, int Hin, int Win, int Hout, int Wout, const int* xbounds,
                                 const int* xk, int xksize, const int* ybounds, const int* yk, int yksize, uint8_t* tmp,

@@ -86,4 +86,15 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return t;
 }
 
+// ragged batches (jpeg.hip, augment.hip): the image element t of the concatenated batch belongs to = the first i with
+// t < prefix[i] (prefix: inclusive, non-decreasing sums of the per-image element counts; t < prefix[B - 1])
+__device__ __forceinline__ int ragged_find(const long* __restrict__ prefix, int B, long t) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (t < prefix[mid]) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
 #define EDITOR_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)

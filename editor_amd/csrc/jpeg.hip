@@ -4,6 +4,9 @@
 //          the scan(s) into quantised DCT coefficient blocks - nothing else;
 //   device (editor_jpeg_reconstruct): dequantisation + 8x8 inverse DCT, chroma upsampling, YCbCr -> RGB and the crop split,
 //          for a whole batch per launch, writing the uint8 (crop, B, H, cw, 3) tensors editor_resize_u8 consumes.
+//          (editor_jpeg_reconstruct_ragged): the same arithmetic for a batch whose files differ in size and sampling - the
+//          separate-file data sets (RGBNT201, MSVR310) - geometry from a device table, output packed image after image for
+//          editor_resize_u8_ragged; still one IDCT launch and one colour launch per batch.
 // The arithmetic restates libjpeg's default decompression path - the one Pillow runs (JDCT_ISLOW, do_fancy_upsampling) -
 // integer for integer, so the pixels are BIT-IDENTICAL to Pillow's (tests/golden/f14_decode.npz):
 //   jidctint.c  jpeg_idct_islow      13-bit constants, two passes, DESCALE rounding, range-limit table
@@ -457,19 +460,10 @@ __device__ __forceinline__ void idct_1d(const int (&in)[8], int (&out)[8], int s
     out[3] = descale(tmp13 + tmp0, shift); out[4] = descale(tmp13 - tmp0, shift);
 }
 
-// one thread per 8x8 block: dequantise, columns (-> scaled by 2^PASS1_BITS), rows, range limit, 8 rows of 8 bytes
-__global__ __launch_bounds__(128) void jpeg_idct_kernel(const int16_t* __restrict__ coef, const uint16_t* __restrict__ qt, JpegGeom g, int B,
-                                                        uint8_t* __restrict__ planes)
+// one 8x8 block: dequantise, columns (-> scaled by 2^PASS1_BITS), rows, range limit, 8 rows of 8 bytes at dst (row pitch pw;
+// dst 8-byte aligned: uint2 stores)
+__device__ __forceinline__ void idct_block(const int16_t* __restrict__ in, const uint16_t* __restrict__ q, uint8_t* __restrict__ dst, int pw)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)B * g.blocks_per_image) return;
-    const int img = (int)(t / g.blocks_per_image);
-    const long bi = t % g.blocks_per_image;
-    const int c = (g.ncomp > 1 && bi >= g.off[1]) ? (bi >= g.off[2] ? 2 : 1) : 0;
-    const long lb = bi - g.off[c];
-    const int by = (int)(lb / g.bw[c]), bx = (int)(lb % g.bw[c]);
-    const int16_t* in = coef + t * 64;
-    const uint16_t* q = qt + ((long)img * 3 + c) * 64;
     int ws[8][8];
 #pragma unroll
     for (int col = 0; col < 8; ++col) {
@@ -480,7 +474,6 @@ __global__ __launch_bounds__(128) void jpeg_idct_kernel(const int16_t* __restric
 #pragma unroll
         for (int r = 0; r < 8; ++r) ws[r][col] = o[r];
     }
-    uint8_t* dst = planes + (long)img * g.plane_bytes + g.plane_off[c] + ((long)by * 8) * g.pw[c] + bx * 8;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         int o[8];
@@ -488,8 +481,33 @@ __global__ __launch_bounds__(128) void jpeg_idct_kernel(const int16_t* __restric
         uint2 pk;
         pk.x = range_limit_centered(o[0]) | (range_limit_centered(o[1]) << 8) | (range_limit_centered(o[2]) << 16) | ((uint32_t)range_limit_centered(o[3]) << 24);
         pk.y = range_limit_centered(o[4]) | (range_limit_centered(o[5]) << 8) | (range_limit_centered(o[6]) << 16) | ((uint32_t)range_limit_centered(o[7]) << 24);
-        *reinterpret_cast<uint2*>(dst + (long)r * g.pw[c]) = pk;
+        *reinterpret_cast<uint2*>(dst + (long)r * pw) = pk;
     }
+}
+
+template <typename T> __device__ __forceinline__ T pick3(const T (&a)[3], int c) { return c == 0 ? a[0] : (c == 1 ? a[1] : a[2]); }
+
+// block `bi` of one image (coefficients at `in`, its three quantisation tables at `q3`) -> its place in the image's planes `pl`
+__device__ __forceinline__ void idct_image_block(const int16_t* __restrict__ in, const uint16_t* __restrict__ q3, const JpegGeom& g, long bi,
+                                                 uint8_t* __restrict__ pl)
+{
+    const int c = (g.ncomp > 1 && bi >= g.off[1]) ? (bi >= g.off[2] ? 2 : 1) : 0;
+    // (selects, not g.x[c]: a geometry built in registers by the ragged kernel would go to scratch under a dynamic index)
+    const long lb = bi - pick3(g.off, c);
+    const int bw = pick3(g.bw, c), pw = pick3(g.pw, c);
+    const int by = (int)(lb / bw), bx = (int)(lb % bw);
+    idct_block(in, q3 + c * 64, pl + pick3(g.plane_off, c) + ((long)by * 8) * pw + bx * 8, pw);
+}
+
+// one thread per 8x8 block of a batch of ONE geometry
+__global__ __launch_bounds__(128) void jpeg_idct_kernel(const int16_t* __restrict__ coef, const uint16_t* __restrict__ qt, JpegGeom g, int B,
+                                                        uint8_t* __restrict__ planes)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)B * g.blocks_per_image) return;
+    const int img = (int)(t / g.blocks_per_image);
+    const long bi = t % g.blocks_per_image;
+    idct_image_block(coef + t * 64, qt + (long)img * 3 * 64, g, bi, planes + (long)img * g.plane_bytes);
 }
 
 __device__ __forceinline__ int clamp255(int x) { return x < 0 ? 0 : (x > 255 ? 255 : x); }
@@ -520,16 +538,10 @@ __device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ p, int pw, 
     return (thiscol * 3 + (3 * r0[cx - 1] + r1[cx - 1]) + 8) >> 4;
 }
 
-// one thread per output pixel: (upsampled) Y, Cb, Cr -> RGB (jdcolor.c ycc_rgb_convert), written into crop x / crop_w of
-// out (ncrop, B, H, crop_w, 3); pixels right of the last whole crop are dropped (bases.py:19-21: range(W // 256))
-__global__ __launch_bounds__(256) void jpeg_color_kernel(const uint8_t* __restrict__ planes, JpegGeom g, int B, int crop_w, int ncrop,
-                                                         uint8_t* __restrict__ out)
+// pixel (x, y) of one image from its planes `pl`: (upsampled) Y, Cb, Cr -> RGB (jdcolor.c ycc_rgb_convert); a lone component
+// is replicated (`convert('RGB')` of a grayscale file)
+__device__ __forceinline__ void color_pixel(const uint8_t* __restrict__ pl, const JpegGeom& g, int x, int y, uint8_t* __restrict__ o)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int wuse = crop_w * ncrop;
-    if (t >= (long)B * g.H * wuse) return;
-    const int x = (int)(t % wuse), y = (int)((t / wuse) % g.H), img = (int)(t / ((long)wuse * g.H));
-    const uint8_t* pl = planes + (long)img * g.plane_bytes;
     const int yv = pl[g.plane_off[0] + (long)y * g.pw[0] + x];
     int r = yv, gg = yv, b = yv;
     if (g.ncomp == 3) {
@@ -545,12 +557,23 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const uint8_t* __restri
             r = yv; gg = cb; b = cr;
         }
     }
-    const int crop = x / crop_w, xc = x % crop_w;
-    uint8_t* o = out + ((((long)crop * B + img) * g.H + y) * crop_w + xc) * 3;
     o[0] = (uint8_t)r; o[1] = (uint8_t)gg; o[2] = (uint8_t)b;
 }
 
-bool make_geom(const int* info, JpegGeom& g)
+// one thread per output pixel, written into crop x / crop_w of out (ncrop, B, H, crop_w, 3); pixels right of the last whole
+// crop are dropped (bases.py:19-21: range(W // 256))
+__global__ __launch_bounds__(256) void jpeg_color_kernel(const uint8_t* __restrict__ planes, JpegGeom g, int B, int crop_w, int ncrop,
+                                                         uint8_t* __restrict__ out)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int wuse = crop_w * ncrop;
+    if (t >= (long)B * g.H * wuse) return;
+    const int x = (int)(t % wuse), y = (int)((t / wuse) % g.H), img = (int)(t / ((long)wuse * g.H));
+    const int crop = x / crop_w, xc = x % crop_w;
+    color_pixel(planes + (long)img * g.plane_bytes, g, x, y, out + ((((long)crop * B + img) * g.H + y) * crop_w + xc) * 3);
+}
+
+__host__ __device__ inline bool make_geom(const int* info, JpegGeom& g)
 {
     g.W = info[0]; g.H = info[1]; g.ncomp = info[2]; g.hmax = info[3]; g.vmax = info[4]; g.mcux = info[5]; g.mcuy = info[6];
     g.transform = info[7];
@@ -567,6 +590,39 @@ bool make_geom(const int* info, JpegGeom& g)
     g.blocks_per_image = off;
     g.plane_bytes = poff;
     return off == info[8];
+}
+
+// ---- ragged batch: every image its own geometry ---------------------------------------------------------------------
+// info: (B,16) int32 rows of editor_jpeg_parse; tab: (5,B) int64 = first coefficient block, plane byte offset (8-byte
+// aligned: uint2 stores), output byte offset, inclusive prefix sum of blocks, inclusive prefix sum of output pixels.
+enum { RT_COEF = 0, RT_PLANE = 1, RT_OUT = 2, RT_BLOCKS = 3, RT_PIXELS = 4, RT_ROWS = 5 };
+
+__global__ __launch_bounds__(128) void jpeg_idct_ragged_kernel(const int16_t* __restrict__ coef, const uint16_t* __restrict__ qt,
+                                                               const int* __restrict__ info, const long* __restrict__ tab, int B, long nblocks,
+                                                               uint8_t* __restrict__ planes)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nblocks) return;
+    const long* prefix = tab + (long)RT_BLOCKS * B;
+    const int img = ragged_find(prefix, B, t);
+    const long bi = t - (img ? prefix[img - 1] : 0);
+    JpegGeom g;
+    make_geom(info + (long)img * 16, g);                               // (validated on the host before the launch)
+    idct_image_block(coef + (tab[(long)RT_COEF * B + img] + bi) * 64, qt + (long)img * 3 * 64, g, bi, planes + tab[(long)RT_PLANE * B + img]);
+}
+
+// one thread per output pixel of the packed output: image i is (H_i, W_i, 3) row-major at its output offset (no crop split)
+__global__ __launch_bounds__(256) void jpeg_color_ragged_kernel(const uint8_t* __restrict__ planes, const int* __restrict__ info,
+                                                                const long* __restrict__ tab, int B, long npixels, uint8_t* __restrict__ out)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= npixels) return;
+    const long* prefix = tab + (long)RT_PIXELS * B;
+    const int img = ragged_find(prefix, B, t);
+    const long p = t - (img ? prefix[img - 1] : 0);
+    JpegGeom g;
+    make_geom(info + (long)img * 16, g);
+    color_pixel(planes + tab[(long)RT_PLANE * B + img], g, (int)(p % g.W), (int)(p / g.W), out + tab[(long)RT_OUT * B + img] + p * 3);
 }
 
 }  // namespace
@@ -620,6 +676,31 @@ extern "C" int editor_jpeg_reconstruct(const int16_t* coef, const uint16_t* qt, 
     EDITOR_LAUNCH_CHECK();
     const long npx = (long)B * g.H * crop_w * ncrop;
     hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, stream, planes, g, B, crop_w, ncrop, out);
+    EDITOR_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int editor_jpeg_reconstruct_ragged(const int16_t* coef, const uint16_t* qt, const int* info_host, const long* tab_host,
+                                              const int* info, const long* tab, int B, uint8_t* planes, uint8_t* out, hipStream_t stream)
+{
+    if (!coef || !qt || !info_host || !tab_host || !info || !tab || !planes || !out || B < 1) return (int)hipErrorInvalidValue;
+    // the kernels trust the tables: every row a geometry make_geom accepts, the prefix sums those geometries' own counts,
+    // offsets non-negative, plane bases 8-byte aligned
+    long blocks = 0, pixels = 0;
+    for (int i = 0; i < B; ++i) {
+        JpegGeom g;
+        if (!make_geom(info_host + (long)i * 16, g)) return (int)hipErrorInvalidValue;
+        if (g.hmax < 1 || g.hmax > 2 || g.vmax < 1 || g.vmax > 2 || (long)g.mcux * 8 * g.hmax < g.W || (long)g.mcuy * 8 * g.vmax < g.H)
+            return (int)hipErrorInvalidValue;                         // (the planes must cover the pixels the colour pass reads)
+        blocks += g.blocks_per_image; pixels += (long)g.W * g.H;
+        const long po = tab_host[(long)RT_PLANE * B + i];
+        if (tab_host[(long)RT_COEF * B + i] < 0 || po < 0 || (po & 7) || tab_host[(long)RT_OUT * B + i] < 0 ||
+            tab_host[(long)RT_BLOCKS * B + i] != blocks || tab_host[(long)RT_PIXELS * B + i] != pixels)
+            return (int)hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(jpeg_idct_ragged_kernel, dim3((unsigned)((blocks + 127) / 128)), dim3(128), 0, stream, coef, qt, info, tab, B, blocks, planes);
+    EDITOR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(jpeg_color_ragged_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, stream, planes, info, tab, B, pixels, out);
     EDITOR_LAUNCH_CHECK();
     return 0;
 }

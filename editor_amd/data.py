@@ -8,8 +8,11 @@ Host side (Python, as in the reference) + one HIP kernel (csrc/augment.hip):
                                from Python's `random`, returned as numbers instead of applied (golden-pinned)
     DeviceTrainTransform       T.RandomHorizontalFlip -> T.Pad -> T.RandomCrop -> T.ToTensor -> T.Normalize ->
                                RandomErasing(mode='pixel') of make_dataloader.py:245-253 for a whole batch in one launch
-Not here: JPEG decode and T.Resize(interpolation=3) (PIL bicubic) stay on the host / in the decoder; the transform takes
-decoded, resized uint8 (B,H,W,3) images.  The flip / crop draws use torch's CPU generator the way torchvision 0.14 does
+    DeviceJpegDecoder / DeviceResize   `Image.open(path).convert('RGB')` + T.Resize: the stitched layout (one 768x128 file, three
+                               256-wide crops: RGBNT100 / RGBNT300) through __call__, the separate-file layout (one detector
+                               crop of any size per modality: RGBNT201 / MSVR310) through decode_ragged + RaggedImages +
+                               load_modalities - a fixed number of launches per batch either way
+The transform takes decoded, resized uint8 (B,H,W,3) images.  The flip / crop draws use torch's CPU generator the way torchvision 0.14 does
 (`torch.rand(1) < p`; `torch.randint(0, h - th + 1)`, then `w`), but torchvision is not installed in the build image, so
 that ORDER is restated from its documentation, not pinned ("parity unpinned" for those two draws only; what the draws do to the
 pixels is pinned to Pillow: tests/golden/f19_flip_pad_crop.npz).
@@ -203,14 +206,125 @@ def resize_coeffs(in_size, out_size, interpolation=3):
     return np.stack([xmin, xmax], axis=1).astype(np.int32), kk
 
 
+class RaggedImages:
+    """A batch of decoded uint8 RGB images of DIFFERENT sizes (the separate-file data sets: one detector crop per modality,
+    data/datasets/bases.py:22-30), packed one after another in one device buffer - what DeviceJpegDecoder.decode_ragged
+    returns and DeviceResize accepts.
+        data     flat uint8 device tensor; image i is (h_i, w_i, 3) row-major at byte offsets[i]
+        offsets  int64 (B + 1), host; offsets[B] = data.numel()
+        sizes    int32 (B, 2) as (h, w), host"""
+
+    def __init__(self, data, offsets, sizes):
+        self.data, self.offsets, self.sizes = data, offsets, sizes
+
+    def __len__(self):
+        return int(self.sizes.shape[0])
+
+    def image(self, i):
+        """-> (h, w, 3) view of image i."""
+        h, w = int(self.sizes[i, 0]), int(self.sizes[i, 1])
+        o = int(self.offsets[i])
+        return self.data[o:o + h * w * 3].view(h, w, 3)
+
+    @classmethod
+    def from_arrays(cls, arrays, device):
+        """list of (H, W, 3) uint8 numpy arrays (a decode of the caller's own) -> RaggedImages on `device`: one H2D copy."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("RaggedImages live on the GPU (no CPU fallback)")
+        arrays = [np.asarray(a) for a in arrays]
+        if not arrays:
+            raise ValueError("RaggedImages: empty batch")
+        for a in arrays:
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+                raise ValueError("RaggedImages: every image is a non-empty (H, W, 3) uint8 array")
+        sizes = np.asarray([a.shape[:2] for a in arrays], dtype=np.int32)
+        offsets = np.concatenate([[0], np.cumsum(sizes[:, 0].astype(np.int64) * sizes[:, 1] * 3)])
+        flat = np.concatenate([a.reshape(-1) for a in arrays])
+        return cls(torch.from_numpy(flat).to(device), torch.from_numpy(offsets), torch.from_numpy(sizes))
+
+
+def ragged_decode_plan(infos):
+    """Where each file of a ragged batch lives in the buffers of editor_jpeg_reconstruct_ragged.  infos: (B,16) int32 rows
+    of editor_jpeg_parse.  -> tab (5,B) int64 = first coefficient block, plane byte offset, output byte offset, inclusive
+    prefix sum of blocks, inclusive prefix sum of output pixels; the totals.  A block is 64 coefficients in and 64 one-byte
+    samples out, so image i's planes start at byte 64 * (its first block): a multiple of 8 (the IDCT stores 8 bytes at a
+    time), and every coefficient base sits on a block boundary."""
+    inf = np.asarray(infos, dtype=np.int64).reshape(-1, 16)
+    blocks, pixels = inf[:, 8], inf[:, 0] * inf[:, 1]
+    bsum, psum = np.cumsum(blocks), np.cumsum(pixels)
+    tab = np.stack([bsum - blocks, 64 * (bsum - blocks), 3 * (psum - pixels), bsum, psum]).astype(np.int64)
+    return tab, int(bsum[-1]), int(psum[-1])
+
+
 class DeviceResize:
-    """T.Resize(size, interpolation) for a batch of decoded uint8 (B,H,W,3) images on the device (editor_resize_u8):
-    bit-exact with what the reference's PIL pipeline produces for the same pixels.  JPEG decode stays on the host."""
+    """T.Resize(size, interpolation) for a batch of decoded uint8 images on the device: a dense (B,H,W,3) tensor
+    (editor_resize_u8) or a RaggedImages batch, every image from its own size (editor_resize_u8_ragged, two launches per
+    batch) -> (B,Hout,Wout,3).  Bit-exact with what the reference's PIL pipeline produces for the same pixels."""
 
     def __init__(self, size, interpolation=3):
         self.size = (int(size[0]), int(size[1]))
         self.interpolation = interpolation
         self._tabs = {}
+        self._rag_index, self._rag_host, self._rag_len, self._rag_dev = {}, [], 0, {}
+
+    def ragged_tables(self, sizes):
+        """Tap tables of a ragged batch.  sizes: (B,2) int (h, w).  -> desc (B,8) int32 rows = h, w, index of the x table in
+        the tap array, its ksize, index of the y table, its ksize, 0, 0.  One table per distinct (input extent, output
+        extent), built once by resize_coeffs and kept: bounds (n_out,2) then taps (n_out,ksize), appended to self.taps()
+        (ksize grows with the downscale factor, hence per image).  An extent equal to its target gets the identity table
+        (one tap of 1 << 22: the byte itself), where Pillow skips the pass."""
+        sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+        desc = np.zeros((sizes.shape[0], 8), dtype=np.int32)
+        desc[:, :2] = sizes
+        for axis, n_out, col in ((1, self.size[1], 2), (0, self.size[0], 4)):
+            uniq, inv = np.unique(sizes[:, axis], return_inverse=True)
+            ent = []
+            for n_in in uniq.tolist():
+                e = self._rag_index.get((n_in, n_out))
+                if e is None:
+                    bounds, k = resize_coeffs(n_in, n_out, self.interpolation)
+                    assert bounds.min() >= 0 and (bounds[:, 1] <= k.shape[1]).all() and (bounds.sum(axis=1) <= n_in).all()
+                    e = self._rag_index[(n_in, n_out)] = (self._rag_len, int(k.shape[1]))
+                    self._rag_host += [bounds.reshape(-1), k.reshape(-1)]
+                    self._rag_len += bounds.size + k.size
+                ent.append(e)
+            desc[:, col:col + 2] = np.asarray(ent, dtype=np.int32)[inv.reshape(-1)]
+        return desc
+
+    def taps(self):
+        """The tap array the desc rows index (int32, host)."""
+        if len(self._rag_host) > 1:
+            self._rag_host = [np.concatenate(self._rag_host)]
+        return self._rag_host[0]
+
+    def _ragged(self, rag):
+        if not rag.data.is_cuda:
+            raise RuntimeError("DeviceResize: images are not on the GPU (no CPU fallback)")
+        b = len(rag)
+        if b < 1:
+            raise ValueError("DeviceResize: empty batch")
+        assert rag.data.dtype == torch.uint8 and rag.data.is_contiguous()
+        oh, ow = self.size
+        dev = rag.data.device
+        sizes = np.asarray(rag.sizes, dtype=np.int64)
+        starts = np.asarray(rag.offsets, dtype=np.int64)[:b]
+        if sizes.shape != (b, 2) or (sizes < 1).any() or (starts < 0).any() or (starts + 3 * sizes[:, 0] * sizes[:, 1] > rag.data.numel()).any():
+            raise ValueError("DeviceResize: RaggedImages sizes / offsets do not fit its data")
+        desc = self.ragged_tables(sizes)
+        hsum = np.cumsum(sizes[:, 0])
+        off = np.stack([starts, 3 * ow * (hsum - sizes[:, 0]), ow * hsum]).astype(np.int64)
+        taps_d = self._rag_dev.get(dev)
+        if taps_d is None or taps_d.numel() != self._rag_len:          # grow-only: re-sent when a new extent added a table
+            taps_d = self._rag_dev[dev] = torch.from_numpy(self.taps()).to(dev)
+        host = np.concatenate([desc.reshape(-1).view(np.uint8), off.reshape(-1).view(np.uint8)])     # one H2D copy for both tables
+        tabs_d = torch.from_numpy(host).to(dev)
+        desc_d, off_d = tabs_d[:32 * b].view(torch.int32), tabs_d[32 * b:].view(torch.int64)
+        tmp = torch.empty(3 * ow * int(hsum[-1]), dtype=torch.uint8, device=dev)
+        out = torch.empty(b, oh, ow, 3, dtype=torch.uint8, device=dev)
+        call("editor_resize_u8_ragged", rag.data, b, oh, ow, ctypes.c_void_p(desc.ctypes.data), ctypes.c_void_p(off.ctypes.data),
+             desc_d, off_d, taps_d, int(taps_d.numel()), tmp, out)
+        return out
 
     def _tables(self, n_in, n_out, device):
         key = (n_in, n_out, device)
@@ -222,6 +336,8 @@ class DeviceResize:
         return t
 
     def __call__(self, images_u8):
+        if isinstance(images_u8, RaggedImages):
+            return self._ragged(images_u8)
         if not images_u8.is_cuda:
             raise RuntimeError("DeviceResize: images are not on the GPU (no CPU fallback)")
         b, h, w, c = images_u8.shape
@@ -282,6 +398,11 @@ class DeviceJpegDecoder:
         crops = dec([open(p, "rb").read() for p in paths], device)     # uint8 (ncrop, B, H, 256, 3): RGB, NI, TI
         x = DeviceResize(cfg.INPUT.SIZE_TRAIN)(crops[0])               # ... the rest of the transform on the device
 
+    Files of DIFFERENT sizes (the separate-file data sets RGBNT201 / MSVR310: one detector crop per modality) go through
+    decode_ragged: any mix of sizes, sampling factors, grayscale, baseline / progressive in one IDCT launch + one colour launch
+    (editor_jpeg_reconstruct_ragged), packed into a RaggedImages that DeviceResize brings to one size.  __call__ keeps
+    refusing such a batch.
+
     Baseline, extended-sequential and progressive Huffman files (round 4) are covered; arithmetic-coded / lossless / 12-bit /
     4-component files raise (EDITOR_JPEG_UNSUPPORTED) and an incomplete progressive file is corrupt: no silent host fallback."""
 
@@ -291,15 +412,23 @@ class DeviceJpegDecoder:
         self.crop_w = int(crop_w)
         self._cd = _lib.lib().cdll
         self._pool = ThreadPoolExecutor(max_workers=max(1, int(threads)))
+        self._arena, self._h2d_done = None, None            # decode_ragged's pinned staging buffer and its last copy's event
+
+    @staticmethod
+    def _refusal(rc):
+        return "JPEG %s (editor_jpeg_parse rc %d)" % ("uses a coding mode the device decoder does not cover "
+                                                      "(arithmetic / lossless / 12-bit / 4 components)" if rc == 9002 else "is corrupt or incomplete", rc)
+
+    def _parse_rc(self, data, info):
+        buf = np.frombuffer(data, dtype=np.uint8)
+        return self._cd.editor_jpeg_parse(ctypes.c_void_p(buf.ctypes.data), len(data), ctypes.c_void_p(info.ctypes.data))
 
     def parse(self, data):
         """-> info (16 int32): W, H, ncomp, hmax, vmax, mcus_x, mcus_y, ycc_transform, blocks_per_image, ..."""
-        buf = np.frombuffer(data, dtype=np.uint8)
         info = np.zeros(16, dtype=np.int32)
-        rc = self._cd.editor_jpeg_parse(ctypes.c_void_p(buf.ctypes.data), len(data), ctypes.c_void_p(info.ctypes.data))
+        rc = self._parse_rc(data, info)
         if rc:
-            raise ValueError("JPEG %s (editor_jpeg_parse rc %d)" % ("uses a coding mode the device decoder does not cover "
-                             "(arithmetic / lossless / 12-bit / 4 components)" if rc == 9002 else "is corrupt or incomplete", rc))
+            raise ValueError(self._refusal(rc))
         return info
 
     def _entropy(self, data, coef_ptr, blocks, qt_ptr, info):
@@ -341,3 +470,88 @@ class DeviceJpegDecoder:
             if n != b:
                 out[:, torch.tensor(idx, device=device)] = dst
         return out
+
+    def _stage(self, nbytes):
+        """The pinned staging buffer of decode_ragged: grow-only and reused across calls (pinning per call costs more than the
+        copy it speeds up), so the previous call's host-to-device copies must have left it before it is written again."""
+        if self._h2d_done is not None:
+            self._h2d_done.synchronize()
+        if self._arena is None or self._arena.numel() < nbytes:
+            self._arena = torch.empty(max(nbytes, 2 * (self._arena.numel() if self._arena is not None else 0)), dtype=torch.uint8).pin_memory()
+        return self._arena
+
+    def decode_ragged(self, files, device):
+        """A batch of JPEG files of ANY mix of sizes / sampling factors / grayscale / baseline / progressive -> RaggedImages
+        (grayscale replicated to three channels, as `convert('RGB')` does).  Every file is parsed before anything is launched: a
+        corrupt or unsupported one raises ValueError naming its index in the batch.  Then the thread pool Huffman-decodes each
+        file into the staging buffer at the file's block offset, three host-to-device copies (coefficients, quantisation tables,
+        descriptor table) and ONE call of the ragged entry: two launches per batch, whatever the sizes."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("DeviceJpegDecoder reconstructs on the GPU (no CPU fallback)")
+        files = list(files)
+        b = len(files)
+        if b < 1:
+            raise ValueError("DeviceJpegDecoder.decode_ragged: empty batch")
+        infos = np.zeros((b, 16), dtype=np.int32)
+        for i, rc in enumerate(self._pool.map(lambda i: self._parse_rc(files[i], infos[i]), range(b))):
+            if rc:
+                raise ValueError("file %d of the batch: %s" % (i, self._refusal(rc)))
+        tab, nblocks, npixels = ragged_decode_plan(infos)
+        n_coef, n_qt, n_info = nblocks * 128, b * 384, b * 64                    # bytes; every region starts 8-byte aligned
+        arena = self._stage(n_coef + n_qt + n_info + tab.nbytes)
+        base = arena.data_ptr()
+        host = arena.numpy()
+        scratch = np.zeros((b, 16), dtype=np.int32)
+
+        def entropy(i):
+            try:
+                self._entropy(files[i], base + int(tab[0, i]) * 128, int(infos[i, 8]), base + n_coef + i * 384, scratch[i])
+            except ValueError as e:
+                raise ValueError("file %d of the batch: %s" % (i, e)) from None
+        list(self._pool.map(entropy, range(b)))
+        o_tab = n_coef + n_qt + n_info
+        host[n_coef + n_qt:o_tab] = infos.reshape(-1).view(np.uint8)
+        host[o_tab:o_tab + tab.nbytes] = tab.reshape(-1).view(np.uint8)
+        with torch.cuda.device(device):
+            coef_d = torch.empty(nblocks * 64, dtype=torch.int16, device=device)
+            qt_d = torch.empty(b * 192, dtype=torch.int16, device=device)        # (uint16 bit patterns)
+            desc_d = torch.empty(n_info + tab.nbytes, dtype=torch.uint8, device=device)
+            coef_d.copy_(arena[:n_coef].view(torch.int16), non_blocking=True)
+            qt_d.copy_(arena[n_coef:n_coef + n_qt].view(torch.int16), non_blocking=True)
+            desc_d.copy_(arena[n_coef + n_qt:o_tab + tab.nbytes], non_blocking=True)
+            self._h2d_done = torch.cuda.Event()
+            self._h2d_done.record()
+            planes = torch.empty(nblocks * 64, dtype=torch.uint8, device=device)
+            data = torch.empty(npixels * 3, dtype=torch.uint8, device=device)
+            call("editor_jpeg_reconstruct_ragged", coef_d, qt_d, ctypes.c_void_p(infos.ctypes.data), ctypes.c_void_p(tab.ctypes.data),
+                 desc_d[:n_info].view(torch.int32), desc_d[n_info:].view(torch.int64), b, planes, data)
+        offsets = np.concatenate([tab[2], [npixels * 3]]).astype(np.int64)
+        sizes = np.ascontiguousarray(infos[:, [1, 0]])
+        return RaggedImages(data, torch.from_numpy(offsets), torch.from_numpy(sizes))
+
+
+_DEFAULT = {}
+
+
+def load_modalities(files_by_modality, size, interpolation=3, device="cuda"):
+    """The separate-file sample layout (RGBNT201 / MSVR310: img_path is a list of one path per modality, each file resized on
+    its own, data/datasets/bases.py:22-30).  files_by_modality: nmod lists of B byte strings -> nmod uint8 (B,Hout,Wout,3)
+    tensors in the order given: ONE ragged decode + ONE ragged resize over all nmod * B files."""
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("load_modalities decodes on the GPU (no CPU fallback)")
+    groups = [list(g) for g in files_by_modality]
+    if not groups or not groups[0]:
+        raise ValueError("load_modalities: empty batch")
+    b = len(groups[0])
+    if any(len(g) != b for g in groups):
+        raise ValueError("load_modalities: every modality lists the same number of files")
+    dec = _DEFAULT.get("decoder")
+    if dec is None:
+        dec = _DEFAULT["decoder"] = DeviceJpegDecoder(crop_w=0, threads=16)
+    key = (int(size[0]), int(size[1]), int(interpolation))
+    rs = _DEFAULT.get(key)
+    if rs is None:
+        rs = _DEFAULT[key] = DeviceResize(size, interpolation)
+    out = rs(dec.decode_ragged([f for g in groups for f in g], device))
+    return [out[m * b:(m + 1) * b] for m in range(len(groups))]

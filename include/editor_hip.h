@@ -503,6 +503,17 @@ int editor_jpeg_planes_bytes(const int* info, long* bytes);
  * B x planes_bytes scratch. */
 int editor_jpeg_reconstruct(const int16_t* coef, const uint16_t* qt, const int* info, int B, uint8_t* planes, int crop_w,
                             uint8_t* out, editor_stream_t stream);
+/* DEVICE, ragged: B images of ANY mix of sizes / sampling factors / grayscale in one IDCT launch + one colour launch (the
+ * separate-file data sets RGBNT201 / MSVR310: one detector crop per modality, data/datasets/bases.py:22-30).  info: (B,16)
+ * int32 rows of editor_jpeg_parse; tab: (5,B) int64 rows = first coefficient block of image i in coef, byte offset of its
+ * sample planes in `planes` (8-byte aligned), byte offset of its pixels in out, INCLUSIVE prefix sum of blocks, INCLUSIVE
+ * prefix sum of output pixels (W * H).  Both tables twice: *_host to validate and size the launches, info / tab the device
+ * copies the kernels read (a thread finds its image by binary search over the prefix row).  qt: (B,3,64).  out: packed,
+ * image i is (H_i, W_i, 3) row-major at its offset; no crop split.  hipErrorInvalidValue for B < 1, a null pointer, a row
+ * make_geom rejects or a table that disagrees with the geometries. */
+int editor_jpeg_reconstruct_ragged(const int16_t* coef, const uint16_t* qt, const int* info_host, const long* tab_host,
+                                   const int* info, const long* tab, int B, uint8_t* planes, uint8_t* out,
+                                   editor_stream_t stream);
 
 /* T.Resize(size, interpolation) of decoded uint8 images (make_dataloader.py:246,256; torchvision 0.14.1 ->
  * PIL.Image.resize = Pillow ImagingResample, 8-bit path): horizontal pass then vertical pass with 22-bit fixed-point taps.
@@ -512,6 +523,16 @@ int editor_jpeg_reconstruct(const int16_t* coef, const uint16_t* qt, const int* 
 int editor_resize_u8(const uint8_t* in, int B, int Hin, int Win, int Hout, int Wout, const int* xbounds, const int* xk,
                      int xksize, const int* ybounds, const int* yk, int yksize, uint8_t* tmp, uint8_t* out,
                      editor_stream_t stream);
+/* The same resize for a RAGGED batch: in is the packed buffer of editor_jpeg_reconstruct_ragged, every image from its own
+ * (H_i, W_i) to one (Hout, Wout), two launches per batch.  desc: (B,8) int32 rows = H_i, W_i, index in `taps` of the x table,
+ * its ksize, index of the y table, its ksize, 0, 0; off: (3,B) int64 rows = byte offset of image i in `in`, byte offset of
+ * its (H_i, Wout, 3) intermediate in tmp, INCLUSIVE prefix sum of H_i * Wout (the horizontal pass's pixels).  taps: int32,
+ * the tables of editor_amd.data.resize_coeffs one after another, each as bounds (n_out,2) then k (n_out,ksize); an axis
+ * that keeps its extent uses its identity table (same bytes as Pillow's skipped pass).  *_host: the host copies, validated.
+ * tmp: 3 * Wout * sum(H_i) bytes.  out: (B,Hout,Wout,3). */
+int editor_resize_u8_ragged(const uint8_t* in, int B, int Hout, int Wout, const int* desc_host, const long* off_host,
+                            const int* desc, const long* off, const int* taps, long ntaps, uint8_t* tmp, uint8_t* out,
+                            editor_stream_t stream);
 
 /* ---- training-step kernels (drop-path RNG of vit_pytorch.py:52-69) ----------------------- */
 

@@ -1,0 +1,111 @@
+"""Separate-file sample layout (RGBNT201 / MSVR310: one detector crop of any size per modality): files/s of the ragged device
+input path beside its host stage and beside the uniform path, on 3 x 128 Pillow-encoded files (4:2:0, quality 75) whose sizes are
+drawn from a seeded spread (about 60x130 to 160x340), resized to 256x128 bicubic:
+    (a) the host stage alone: parse + Huffman decode of every file on 16 threads (no device work)
+    (b) DeviceJpegDecoder.decode_ragged + DeviceResize on the RaggedImages, end to end (host clock, ends in a synchronise)
+    (c) the yardstick: DeviceJpegDecoder.__call__ + DeviceResize on 384 files of ONE size with the same total pixel count
+and (b) against the 9 400 files/s the benchmarked tri-modal step consumes (about 3 100 img/s x 3 files).
+    python tools/ragged_input_time.py [--reps 10]"""
+import argparse
+import ctypes
+import io
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from editor_amd.data import DeviceJpegDecoder, DeviceResize      # noqa: E402
+
+STEP_FILES_PER_S = 9400.0
+SIZE = (256, 128)
+
+
+def encode(rng, w, h):
+    from PIL import Image
+    yy, xx = np.mgrid[0:h, 0:w]
+    base = np.stack([128 + 100 * np.sin(xx / 17.0) * np.cos(yy / 11.0), 128 + 90 * np.cos(xx / 29.0 + yy / 7.0),
+                     255.0 * (xx + yy) / (w + h)], axis=2) + rng.normal(0, 12, (h, w, 3))
+    bio = io.BytesIO()
+    Image.fromarray(np.clip(base, 0, 255).astype(np.uint8)).save(bio, "JPEG", quality=75, subsampling=2)
+    return bio.getvalue()
+
+
+def wall(fn, reps, warmup=2):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    a = ap.parse_args()
+    rng = np.random.default_rng(201)
+    n = 3 * 128
+    ws, hs = rng.integers(60, 161, n), rng.integers(130, 341, n)
+    ragged = [encode(rng, int(w), int(h)) for w, h in zip(ws, hs)]
+    pixels = int((ws * hs).sum())
+    uw = int(round(np.sqrt(pixels / n / 2.0)))                    # one size, aspect 1:2 like the spread's centre, same total pixel count
+    uh = int(round(pixels / n / uw))
+    uniform = [encode(rng, uw, uh) for _ in range(n)]
+    print("files: %d ragged (%.1f Mpixel, %.1f MB of JPEG) | %d uniform %dx%d (%.1f Mpixel, %.1f MB)"
+          % (n, pixels / 1e6, sum(map(len, ragged)) / 1e6, n, uw, uh, n * uw * uh / 1e6, sum(map(len, uniform)) / 1e6))
+
+    dec = DeviceJpegDecoder(crop_w=0, threads=16)
+    rs = DeviceResize(SIZE, 3)
+
+    # (a) the host stage alone
+    infos = np.stack([dec.parse(f) for f in ragged])
+    first = np.concatenate([[0], np.cumsum(infos[:, 8].astype(np.int64))])
+    coef = np.zeros((int(first[-1]), 64), dtype=np.int16)
+    qt = np.zeros((n, 192), dtype=np.uint16)
+    scratch = np.zeros((n, 16), dtype=np.int32)
+
+    def host_stage():
+        list(dec._pool.map(lambda i: dec._parse_rc(ragged[i], scratch[i]), range(n)))
+        list(dec._pool.map(lambda i: dec._entropy(ragged[i], coef.ctypes.data + int(first[i]) * 128, int(infos[i, 8]),
+                                                  qt.ctypes.data + i * 384, scratch[i]), range(n)))
+    t_a = wall(host_stage, a.reps)
+
+    # (b) ragged decode + resize, (c) uniform decode + resize
+    def run_ragged():
+        return rs(dec.decode_ragged(ragged, "cuda"))
+
+    def run_uniform():
+        return rs(dec(uniform, "cuda")[0])
+    t_b = wall(run_ragged, a.reps)
+    t_c = wall(run_uniform, a.reps)
+    t_b2 = wall(run_ragged, a.reps)                               # again after (c): the spread between the two is the noise
+    # the device share of (b): the two entries alone, inputs already on the device
+    rag = dec.decode_ragged(ragged, "cuda")
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    rs(rag)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(a.reps):
+        rs(rag)
+    e1.record()
+    torch.cuda.synchronize()
+    t_rs = e0.elapsed_time(e1) / a.reps / 1e3
+
+    out = run_ragged()
+    assert tuple(out.shape) == (n,) + SIZE + (3,)
+    for name, t in (("(a) host parse + Huffman, 16 threads", t_a), ("(b) ragged decode + resize, end to end", t_b),
+                    ("(b) again", t_b2), ("(c) uniform decode + resize, end to end", t_c)):
+        print("%-44s %8.2f ms / batch  %9.0f files/s" % (name, 1e3 * t, n / t))
+    print("%-44s %8.2f ms / batch  (host table building + 2 launches, stream time)" % ("    ragged resize alone", 1e3 * t_rs))
+    best_b = min(t_b, t_b2)
+    print("(b) / step demand (%.0f files/s): x %.2f   (b) / (c): x %.2f   (a) / (b): x %.2f of (b)'s time is the host stage"
+          % (STEP_FILES_PER_S, n / best_b / STEP_FILES_PER_S, t_c / best_b, t_a / best_b))
+
+
+if __name__ == "__main__":
+    main()

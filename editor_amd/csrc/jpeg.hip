@@ -7,6 +7,9 @@
 //          (editor_jpeg_reconstruct_ragged): the same arithmetic for a batch whose files differ in size and sampling - the
 //          separate-file data sets (RGBNT201, MSVR310) - geometry from a device table, output packed image after image for
 //          editor_resize_u8_ragged; still one IDCT launch and one colour launch per batch.
+//          (editor_jpeg_entropy_device, with its planner editor_jpeg_plan and host twin editor_jpeg_entropy_segments): the
+//          Huffman decode itself for files with one whole-frame sequential scan, one wave per restart segment of the batch, so
+//          such files cross the bus as compressed bytes (DeviceJpegDecoder(entropy="device"); the host decode stays the default).
 // The arithmetic restates libjpeg's default decompression path - the one Pillow runs (JDCT_ISLOW, do_fancy_upsampling) -
 // integer for integer, so the pixels are BIT-IDENTICAL to Pillow's (tests/golden/f14_decode.npz):
 //   jidctint.c  jpeg_idct_islow      13-bit constants, two passes, DESCALE rounding, range-limit table
@@ -33,6 +36,7 @@ const uint8_t kZigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4
 
 struct HuffTab {
     bool present = false;
+    uint8_t bits[17]; int nvals = 0;   // the compact DHT form (what the scan planner hands to the device)
     uint8_t vals[256];
     int maxcode[18];          // largest code of each length (-1: none)
     int valoff[17];           // vals index of the first code of each length minus that code
@@ -44,6 +48,7 @@ bool build_huff(HuffTab& t, const uint8_t* bits /* [1..16] */, const uint8_t* va
     int code = 0, k = 0;
     memset(t.look, 0, sizeof(t.look));
     memcpy(t.vals, vals, nvals);
+    memcpy(t.bits, bits, 17); t.nvals = nvals;
     for (int l = 1; l <= 16; ++l) {
         t.valoff[l] = k - code;
         for (int i = 0; i < bits[l]; ++i, ++k, ++code) {
@@ -107,6 +112,19 @@ inline int extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 :
 
 struct Comp { int id, hs, vs, tq, td, ta; int bw, bh; long off; };
 
+// What editor_jpeg_plan records at the FIRST scan header of a headers-only walk: the state a sequential scan decodes with
+// (tables and restart interval as they stand THERE, not at the end of the file) and where its entropy-coded bytes begin.
+enum { DHT_BYTES = 272 };                          // 16 length counts + up to 256 values
+struct ScanPlan {
+    int nsos = 0;
+    bool whole_frame_in_order = false;             // one interleaved scan naming every component in frame order (or the lone one)
+    bool tables_present = false;                   // every quantisation / Huffman table the scan names has been defined
+    long ecs = 0;                                  // first entropy-coded byte
+    int restart = 0;
+    int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
+    uint8_t dht[8][DHT_BYTES];                     // DC tables 0..3, AC tables 0..3; only the ones the scan names are filled
+};
+
 struct Jpeg {
     int W = 0, H = 0, ncomp = 0, hmax = 1, vmax = 1, mcux = 0, mcuy = 0;
     Comp comp[3];
@@ -118,7 +136,34 @@ struct Jpeg {
     long total_blocks = 0;
     bool covered[3] = {false, false, false};      // components some scan has delivered
     int8_t coef_al[3][64];                        // progressive: successive-approximation bit each coefficient has reached (-1: none yet)
+    ScanPlan* plan = nullptr;                     // headers-only walks of editor_jpeg_plan
 };
+
+void dht_compact(const HuffTab& t, uint8_t* out)
+{
+    memset(out, 0, DHT_BYTES);
+    if (!t.present) return;
+    memcpy(out, t.bits + 1, 16);
+    memcpy(out + 16, t.vals, t.nvals);
+}
+
+void record_scan(const Jpeg& j, int ns, const int* idx, long ecs)
+{
+    ScanPlan& p = *j.plan;
+    if (++p.nsos != 1) return;
+    p.ecs = ecs; p.restart = j.restart;
+    p.whole_frame_in_order = ns == j.ncomp;
+    p.tables_present = true;
+    memset(p.dht, 0, sizeof(p.dht));
+    for (int i = 0; i < ns; ++i) {
+        const Comp& k = j.comp[idx[i]];
+        if (idx[i] != i) p.whole_frame_in_order = false;
+        if (!j.qt_ok[k.tq] || !j.dc[k.td].present || !j.ac[k.ta].present) p.tables_present = false;
+        if (idx[i] == i) { p.td[i] = k.td; p.ta[i] = k.ta; }
+        dht_compact(j.dc[k.td], p.dht[k.td]);
+        dht_compact(j.ac[k.ta], p.dht[4 + k.ta]);
+    }
+}
 
 inline int rd16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
@@ -216,6 +261,7 @@ int decode(const uint8_t* d, long n, Jpeg& j, int16_t* coef, long coef_blocks)
             pos += 2 + len;
             seen_scan = true;
             if (!coef) {                                                  // headers only: skip the entropy-coded segment
+                if (j.plan) record_scan(j, ns, idx, pos);
                 while (pos + 1 < n && !(d[pos] == 0xFF && d[pos + 1] != 0x00 && !(d[pos + 1] >= 0xD0 && d[pos + 1] <= 0xD7))) ++pos;
                 continue;
             }
@@ -625,6 +671,299 @@ __global__ __launch_bounds__(256) void jpeg_color_ragged_kernel(const uint8_t* _
     color_pixel(planes + tab[(long)RT_PLANE * B + img], g, (int)(p % g.W), (int)(p / g.W), out + tab[(long)RT_OUT * B + img] + p * 3);
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------
+// sequential-scan entropy decode, one restart segment at a time: ONE routine for the host twin and the device kernel
+// ------------------------------------------------------------------------------------------------------------------
+// A device-eligible file (editor_jpeg_plan) has one interleaved scan whose restart markers split it into segments that
+// decode independently: the DC predictors and the bit reader start afresh at each.  decode() walks such a scan MCU by MCU
+// and resynchronises at every RSTn; for a scan with exactly the expected markers that is the same as decoding every
+// segment on its own between the planner's byte ranges, which is what happens here.
+//   bytes    every read is bounded by the segment's end (and by what the caller has staged); past it, zeros are fed
+//   writes   the destination block is computed from the block's index in the segment and the geometry - never from data
+//   loops    block loop: counted from the geometry; coefficient loop: index strictly increases to 64
+// (the kernel's copy of kZigzag; it keeps it in LDS - a load from here per coefficient would sit on the walking lane's critical path)
+__device__ __attribute__((unused)) const uint8_t kZigzagDev[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                                           35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+// The decoder's view of one Huffman table, derived from the compact DHT form (HuffTab without the host-only fields).
+struct HuffLut {
+    uint16_t look[512];       // 9-bit lookahead: (length << 8) | symbol, 0 = longer code
+    int maxcode[18];
+    int valoff[18];
+    uint8_t vals[256];
+};
+
+// first: the per-length rows (one caller per table) ...
+__host__ __device__ inline void lut_lengths(HuffLut& t, const uint8_t* dht)
+{
+    int code = 0, k = 0;
+    t.maxcode[0] = -1; t.valoff[0] = 0;
+    for (int l = 1; l <= 16; ++l) {
+        const int nb = dht[l - 1];
+        t.valoff[l] = k - code;
+        code += nb; k += nb;
+        t.maxcode[l] = nb ? code - 1 : -1;
+        code <<= 1;
+    }
+    t.maxcode[17] = 0x7fffffff; t.valoff[17] = 0;
+}
+// ... then, with those visible, the values and the lookahead entries, `nlanes` callers striding over them.  Entry p is the
+// canonical decode of its own 9 bits, which is what build_huff's fill leaves there for a table that passed its check (the
+// planner ran it); the value index is masked, so a table that did not cannot be read out of range either.
+__host__ __device__ inline void lut_fill(HuffLut& t, const uint8_t* dht, int lane, int nlanes)
+{
+    for (int i = lane; i < 256; i += nlanes) t.vals[i] = dht[16 + i];
+    for (int p = lane; p < 512; p += nlanes) {
+        int e = 0;
+        for (int l = 1; l <= 9; ++l) {
+            const int c = p >> (9 - l);
+            if (c <= t.maxcode[l]) { e = (l << 8) | dht[16 + ((c + t.valoff[l]) & 0xff)]; break; }
+        }
+        t.look[p] = (uint16_t)e;
+    }
+}
+
+// BitReader over a WINDOW of the stream: buf[0] is stream byte `base`, bytes [base, lim) are present.  The host hands the
+// whole stream (base 0, lim = its length); the kernel restages the window between blocks (SEG_MARGIN).
+struct SegReader {
+    const uint8_t* buf; long base, lim;
+    long p, end;                                   // next byte; end of the segment
+    uint64_t acc; int nbits; bool marker;
+    // Feeds the bytes BitReader::fill feeds, in the same order; only how far ahead it reads differs (25 to 56 bits, enough
+    // for any peek), which no decoded value depends on.  Four bytes at once where none of them is 0xFF: the four reads are
+    // independent, the byte-by-byte path below waits for each before it knows where the next one is.
+    __host__ __device__ __forceinline__ void fill() {
+        while (nbits <= 24) {
+            if (!marker && p >= base && p + 4 <= end && p + 4 <= lim) {
+                const uint8_t* q = buf + (p - base);
+                const uint32_t b0 = q[0], b1 = q[1], b2 = q[2], b3 = q[3];
+                if (b0 != 0xFF && b1 != 0xFF && b2 != 0xFF && b3 != 0xFF) {
+                    acc = (acc << 32) | ((b0 << 24) | (b1 << 16) | (b2 << 8) | b3);
+                    nbits += 32; p += 4;
+                    continue;
+                }
+            }
+            uint8_t b = 0;
+            if (!marker && p < end && p >= base && p < lim) {
+                b = buf[p - base];
+                if (b == 0xFF) {
+                    if (p + 1 < end && p + 1 < lim && buf[p + 1 - base] == 0x00) p += 2;
+                    else { marker = true; b = 0; }
+                } else ++p;
+            } else {
+                marker = true;
+            }
+            acc = (acc << 8) | b;
+            nbits += 8;
+        }
+    }
+    __host__ __device__ __forceinline__ int peek(int n) { if (nbits < n) fill(); return (int)((acc >> (nbits - n)) & ((1u << n) - 1)); }
+    __host__ __device__ __forceinline__ void drop(int n) { nbits -= n; }
+    __host__ __device__ __forceinline__ int get(int n) { if (n == 0) return 0; const int v = peek(n); drop(n); return v; }
+};
+
+__host__ __device__ __forceinline__ int seg_huff(SegReader& br, const HuffLut& t)
+{
+    const int e = t.look[br.peek(9)];
+    if (e) { br.drop(e >> 8); return e & 0xff; }
+    const int code = br.peek(16);
+    for (int l = 10; l <= 16; ++l) {
+        const int c = code >> (16 - l);
+        if (c <= t.maxcode[l]) { br.drop(l); return t.vals[(c + t.valoff[l]) & 0xff]; }
+    }
+    br.drop(16);
+    return -1;
+}
+__host__ __device__ __forceinline__ int seg_extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
+
+// Geometry of a device-eligible scan (decode()'s accepted layouts: luma hmax x vmax blocks per MCU, chroma 1 x 1).
+struct ScanGeom {
+    int ncomp, hmax, vmax, mcux, mcuy, restart;
+    int hv, bpm;                                   // luma blocks per MCU; blocks per MCU
+    long nmcu, total_blocks, off1, off2;
+};
+__host__ __device__ inline bool make_scan_geom(const int* fd, ScanGeom& g)
+{
+    g.ncomp = fd[0]; g.hmax = fd[1]; g.vmax = fd[2]; g.mcux = fd[3]; g.mcuy = fd[4]; g.restart = fd[5];
+    if ((g.ncomp != 1 && g.ncomp != 3) || g.hmax < 1 || g.hmax > 2 || g.vmax < 1 || g.vmax > 2 || (g.hmax == 1 && g.vmax == 2) ||
+        (g.ncomp == 1 && g.hmax * g.vmax != 1) || g.mcux < 1 || g.mcux > 8192 || g.mcuy < 1 || g.mcuy > 8192 || g.restart < 0 || g.restart > 65535)
+        return false;
+    g.hv = g.hmax * g.vmax; g.bpm = g.ncomp == 3 ? g.hv + 2 : 1;
+    g.nmcu = (long)g.mcux * g.mcuy;
+    g.off1 = g.nmcu * g.hv; g.off2 = g.off1 + g.nmcu;
+    g.total_blocks = g.ncomp == 3 ? g.off2 + g.nmcu : g.nmcu;
+    return true;
+}
+// block `b` (MCU-major, as the scan delivers them) of the segment whose first MCU is m0 -> its block in the image and its
+// component.  m0 * bpm + b < nmcu * bpm (the callers' loop bound) puts the result inside [0, total_blocks).
+__host__ __device__ __forceinline__ long scan_block(const ScanGeom& g, long m0, long b, int& c)
+{
+    const long mcu = m0 + b / g.bpm;
+    const int w = (int)(b % g.bpm);
+    const long my = mcu / g.mcux, mx = mcu % g.mcux;
+    if (w < g.hv) { c = 0; return (my * g.vmax + w / g.hmax) * ((long)g.mcux * g.hmax) + mx * g.hmax + w % g.hmax; }
+    c = 1 + w - g.hv;
+    return (c == 1 ? g.off1 : g.off2) + my * g.mcux + mx;
+}
+
+enum { SEG_DONE = 0, SEG_REFILL = -1 };
+enum { SEG_WINDOW = 4096, SEG_MARGIN = 528 };
+// (a block is at most a 16-bit code + 11 bits, then 63 x (16-bit code + 15 bits): 1980 bits = 248 bytes, 496 with every
+//  byte stuffed, and the reader runs at most 8 bytes - 16 stuffed - ahead: a block that starts SEG_MARGIN bytes before the
+//  window's end never reaches it)
+struct SegState {
+    long blk;                                      // next block of the segment
+    int pred0, pred1, pred2;
+    SegReader br;
+};
+
+// Decodes blocks [st.blk, nblk) of one segment into `img` (the image's own block range, ZERO-FILLED by the caller: only
+// non-zero positions are written).  lut[c] / lut[3 + c]: DC / AC table of component c; zigzag: kZigzag, where the caller
+// keeps it.  -> SEG_DONE, EDITOR_JPEG_CORRUPT (code not found, DC size above 11, index past 63 - decode()'s three), or
+// SEG_REFILL when the window ends before the segment does and the next block might cross it (st then names the byte to
+// restage from).
+__host__ __device__ __forceinline__ int decode_segment_blocks(SegState& st, const ScanGeom& g, const HuffLut* lut, const uint8_t* zigzag, int16_t* img,
+                                                              long m0, long nblk)
+{
+    SegReader& br = st.br;
+    while (st.blk < nblk) {
+        if (br.lim < br.end && br.p + SEG_MARGIN > br.lim) return SEG_REFILL;
+        int c;
+        const long dst = scan_block(g, m0, st.blk, c);
+        if (dst < 0 || dst >= g.total_blocks) return EDITOR_JPEG_CORRUPT;     // (cannot happen: see scan_block)
+        int16_t* blk = img + dst * 64;
+        const int sdc = seg_huff(br, lut[c]);
+        if (sdc < 0 || sdc > 11) return EDITOR_JPEG_CORRUPT;
+        const int diff = sdc ? seg_extend(br.get(sdc), sdc) : 0;
+        int pred = (c == 0 ? st.pred0 : (c == 1 ? st.pred1 : st.pred2)) + diff;
+        if (c == 0) st.pred0 = pred; else if (c == 1) st.pred1 = pred; else st.pred2 = pred;
+        blk[0] = (int16_t)pred;
+        const HuffLut& ac = lut[3 + c];
+        for (int kk = 1; kk < 64;) {
+            const int rs = seg_huff(br, ac);
+            if (rs < 0) return EDITOR_JPEG_CORRUPT;
+            const int r = rs >> 4, sz = rs & 15;
+            if (sz == 0) { if (r == 15) { kk += 16; continue; } break; }
+            kk += r;
+            if (kk > 63) return EDITOR_JPEG_CORRUPT;
+            blk[zigzag[kk]] = (int16_t)seg_extend(br.get(sz), sz);      // (kk <= 63 checked above)
+            ++kk;
+        }
+        ++st.blk;
+    }
+    return SEG_DONE;
+}
+
+__host__ __device__ __forceinline__ void seg_begin(SegState& st, long start, long end)
+{
+    st.blk = 0; st.pred0 = st.pred1 = st.pred2 = 0;
+    st.br.p = start; st.br.end = end; st.br.acc = 0; st.br.nbits = 0; st.br.marker = false;
+}
+
+// Descriptor tables of a planned batch (host and device entries take the same ones):
+//   fdesc (B,16) int32   ncomp, hmax, vmax, mcus_x, mcus_y, restart interval, DC table of component 0..2, AC table of 0..2
+//                        (rows of the batch's table pool `huff`, nhuff x 272 bytes)
+//   ftab  (3,B)  int64   first coefficient block; where byte 0 of the FILE would sit in `bytes` (only the scan's bytes need
+//                        be there, so this may be negative); INCLUSIVE prefix sum of segments (a host-decoded file: none)
+//   seg   (S,3)  int64   [byte start, byte end) in the file, first MCU
+enum { FT_COEF = 0, FT_BYTE = 1, FT_SEGS = 2, FT_ROWS = 3 };
+
+// Everything the segment decoder trusts, checked on the host copies before anything runs.
+bool check_entropy_tables(long nbytes, const int* fdesc, const long* ftab, const long* seg, int nhuff, int B, long nseg, long coef_blocks)
+{
+    if (nbytes < 0 || B < 1 || nseg < 0 || nhuff < 1 || coef_blocks < 0) return false;
+    long done = 0;
+    for (int f = 0; f < B; ++f) {
+        const long upto = ftab[(long)FT_SEGS * B + f];
+        const long ns = upto - done;
+        if (ns < 0 || upto > nseg) return false;
+        if (ns == 0) continue;
+        ScanGeom g;
+        const int* fd = fdesc + (long)f * 16;
+        if (!make_scan_geom(fd, g)) return false;
+        for (int c = 0; c < g.ncomp; ++c)
+            if (fd[6 + c] < 0 || fd[6 + c] >= nhuff || fd[9 + c] < 0 || fd[9 + c] >= nhuff) return false;
+        const long co = ftab[(long)FT_COEF * B + f], bo = ftab[(long)FT_BYTE * B + f];
+        if (co < 0 || co > coef_blocks || g.total_blocks > coef_blocks - co) return false;
+        // the segments cover every MCU once: segment k starts at MCU k * Ri
+        if (ns != (g.restart ? (g.nmcu + g.restart - 1) / g.restart : 1)) return false;
+        for (long k = 0; k < ns; ++k) {
+            const long* s = seg + (done + k) * 3;
+            if (s[2] != k * g.restart || s[0] > s[1] || bo > nbytes || s[0] < -bo || s[1] > nbytes - bo) return false;
+        }
+        done = upto;
+    }
+    return done == nseg;
+}
+
+// one 64-thread workgroup (one wave) per restart segment of the whole batch
+__global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restrict__ bytes, long nbytes, const int* __restrict__ fdesc,
+                                                          const long* __restrict__ ftab, const long* __restrict__ seg,
+                                                          const uint8_t* __restrict__ huff, int B, long nseg, int16_t* __restrict__ coef,
+                                                          int* __restrict__ status)
+{
+    __shared__ HuffLut lut[6];
+    __shared__ __attribute__((aligned(16))) uint8_t win[SEG_WINDOW];
+    __shared__ uint8_t zigzag[64];
+    __shared__ long next_pos;
+    __shared__ int verdict;
+    const long s = blockIdx.x;
+    if (s >= nseg) return;
+    const int lane = threadIdx.x;
+    const int f = ragged_find(ftab + (long)FT_SEGS * B, B, s);
+    const int* fd = fdesc + (long)f * 16;
+    ScanGeom g;
+    if (!make_scan_geom(fd, g)) return;                                   // (validated on the host before the launch)
+    const long m0 = seg[s * 3 + 2];
+    const long m1 = g.restart && m0 + g.restart < g.nmcu ? m0 + g.restart : g.nmcu;
+    const long nblk = (m1 - m0) * g.bpm;
+    const long bo = ftab[(long)FT_BYTE * B + f];
+    const long start = bo + seg[s * 3], end = bo + seg[s * 3 + 1];        // in `bytes`
+    int16_t* img = coef + ftab[(long)FT_COEF * B + f] * 64;
+
+    // the lookahead tables of this file's scan, all lanes
+    zigzag[lane] = kZigzagDev[lane];
+    const bool mine = lane < 6 && lane % 3 < g.ncomp;
+    if (mine) lut_lengths(lut[lane], huff + (long)fd[6 + lane] * DHT_BYTES);
+    __syncthreads();
+    for (int t = 0; t < 6; ++t)
+        if (t % 3 < g.ncomp) lut_fill(lut[t], huff + (long)fd[6 + t] * DHT_BYTES, lane, EDITOR_WAVE);
+    // zero the segment's blocks, 16 bytes per lane
+    for (long i = lane; i < nblk * 8; i += EDITOR_WAVE) {
+        int c;
+        const long dst = scan_block(g, m0, i >> 3, c);
+        *reinterpret_cast<uint4*>(img + dst * 64 + (i & 7) * 8) = make_uint4(0, 0, 0, 0);
+    }
+    __threadfence_block();
+    __syncthreads();
+
+    SegState st;
+    seg_begin(st, start, end);
+    long wpos = start & ~15L;
+    int rc = SEG_REFILL;
+    for (long round = 0; round <= nblk && rc == SEG_REFILL; ++round) {   // (every round decodes at least one block)
+        const long need = end - wpos < SEG_WINDOW ? end - wpos : SEG_WINDOW;   // (the reader stops at the segment's end)
+        for (int i = lane * 16; i < need; i += EDITOR_WAVE * 16) {
+            const long a = wpos + i;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (a >= 0 && a + 16 <= nbytes) v = *reinterpret_cast<const uint4*>(bytes + a);
+            *reinterpret_cast<uint4*>(win + i) = v;
+        }
+        __syncthreads();
+        if (lane == 0) {                                                  // one lane walks the bits
+            st.br.buf = win; st.br.base = wpos;
+            st.br.lim = wpos + SEG_WINDOW < nbytes ? wpos + SEG_WINDOW : nbytes;
+            verdict = decode_segment_blocks(st, g, lut, zigzag, img, m0, nblk);
+            next_pos = st.br.p;
+        }
+        __syncthreads();
+        rc = verdict;
+        wpos = next_pos & ~15L;
+        __syncthreads();
+    }
+    if (lane == 0 && rc != SEG_DONE) status[f] = EDITOR_JPEG_CORRUPT;
+}
+
 }  // namespace
 
 extern "C" int editor_jpeg_parse(const uint8_t* data, long n, int* info)
@@ -701,6 +1040,105 @@ extern "C" int editor_jpeg_reconstruct_ragged(const int16_t* coef, const uint16_
     hipLaunchKernelGGL(jpeg_idct_ragged_kernel, dim3((unsigned)((blocks + 127) / 128)), dim3(128), 0, stream, coef, qt, info, tab, B, blocks, planes);
     EDITOR_LAUNCH_CHECK();
     hipLaunchKernelGGL(jpeg_color_ragged_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, stream, planes, info, tab, B, pixels, out);
+    EDITOR_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- device-side entropy decode of sequential scans ----------------------------------------------------------------
+extern "C" int editor_jpeg_plan(const uint8_t* data, long n, int* info, int* plan, uint16_t* qt, uint8_t* huff, long* seg, long seg_cap)
+{
+    if (!data || !info || !plan || !qt || !huff || (!seg && seg_cap > 0)) return EDITOR_JPEG_CORRUPT;
+    Jpeg j;
+    ScanPlan sp;
+    j.plan = &sp;
+    const int rc = decode(data, n, j, nullptr, 0);
+    if (rc) return rc;
+    fill_info(j, info);
+    for (int c = 0; c < 3; ++c)
+        for (int i = 0; i < 64; ++i) qt[c * 64 + i] = c < j.ncomp ? j.qt[j.comp[c].tq][i] : 1;
+    memcpy(huff, sp.dht, sizeof(sp.dht));
+    // one pass over the first scan's entropy-coded bytes; a byte after 0xFF is classified as BitReader::fill does: 00 is a
+    // stuffed data byte, anything else (or nothing) ends the data - an RSTn ends a segment, the rest end the scan
+    const long nmcu = (long)j.mcux * j.mcuy;
+    long p = sp.ecs, seg_start = sp.ecs, nseg = 0, markers = 0, end = n;
+    bool cyclic = true;
+    while (p < n) {
+        const uint8_t* ff = (const uint8_t*)memchr(data + p, 0xFF, (size_t)(n - p));
+        if (!ff) break;
+        p = ff - data;
+        if (p + 1 < n && data[p + 1] == 0x00) { p += 2; continue; }
+        if (p + 1 < n && data[p + 1] >= 0xD0 && data[p + 1] <= 0xD7) {
+            if (nseg < seg_cap) { seg[nseg * 3] = seg_start; seg[nseg * 3 + 1] = p; seg[nseg * 3 + 2] = nseg * sp.restart; }
+            if (data[p + 1] != 0xD0 + (markers & 7)) cyclic = false;
+            ++nseg; ++markers;
+            p += 2; seg_start = p;
+            continue;
+        }
+        end = p;
+        break;
+    }
+    if (nseg < seg_cap) { seg[nseg * 3] = seg_start; seg[nseg * 3 + 1] = end; seg[nseg * 3 + 2] = nseg * sp.restart; }
+    ++nseg;
+    const long expect = sp.restart ? (nmcu + sp.restart - 1) / sp.restart - 1 : 0;
+    const bool eligible = !j.progressive && sp.nsos == 1 && sp.whole_frame_in_order && sp.tables_present && markers == expect && cyclic;
+    memset(plan, 0, 16 * sizeof(int));
+    plan[0] = eligible; plan[1] = (int)(nseg > 0x7fffffff ? 0x7fffffff : nseg); plan[2] = sp.restart; plan[3] = (int)nmcu;
+    for (int c = 0; c < 3; ++c) { plan[4 + c] = sp.td[c]; plan[7 + c] = sp.ta[c]; }
+    plan[10] = sp.nsos;
+    return 0;
+}
+
+extern "C" int editor_jpeg_entropy_segments(const uint8_t* bytes, long nbytes, const int* fdesc, const long* ftab, const long* seg,
+                                            const uint8_t* huff, int nhuff, int B, long nseg, int16_t* coef, long coef_blocks, int* status)
+{
+    if (!bytes || !fdesc || !ftab || !seg || !huff || !coef || !status) return (int)hipErrorInvalidValue;
+    if (!check_entropy_tables(nbytes, fdesc, ftab, seg, nhuff, B, nseg, coef_blocks)) return (int)hipErrorInvalidValue;
+    HuffLut lut[6];
+    long done = 0;
+    for (int f = 0; f < B; ++f) {
+        status[f] = 0;
+        const long upto = ftab[(long)FT_SEGS * B + f];
+        if (upto == done) continue;
+        const int* fd = fdesc + (long)f * 16;
+        ScanGeom g;
+        make_scan_geom(fd, g);
+        for (int t = 0; t < 6; ++t)
+            if (t % 3 < g.ncomp) {
+                const uint8_t* dht = huff + (long)fd[6 + t] * DHT_BYTES;
+                lut_lengths(lut[t], dht);
+                lut_fill(lut[t], dht, 0, 1);
+            }
+        int16_t* img = coef + ftab[(long)FT_COEF * B + f] * 64;
+        memset(img, 0, (size_t)g.total_blocks * 128);
+        const long bo = ftab[(long)FT_BYTE * B + f];
+        for (long s = done; s < upto; ++s) {
+            const long m0 = seg[s * 3 + 2];
+            const long m1 = g.restart && m0 + g.restart < g.nmcu ? m0 + g.restart : g.nmcu;
+            SegState st;
+            seg_begin(st, bo + seg[s * 3], bo + seg[s * 3 + 1]);
+            st.br.buf = bytes; st.br.base = 0; st.br.lim = nbytes;
+            if (decode_segment_blocks(st, g, lut, kZigzag, img, m0, (m1 - m0) * g.bpm) != SEG_DONE) status[f] = EDITOR_JPEG_CORRUPT;
+        }
+        done = upto;
+    }
+    return 0;
+}
+
+extern "C" int editor_jpeg_entropy_device(const uint8_t* bytes, long nbytes, const int* fdesc_host, const long* ftab_host, const long* seg_host,
+                                          const int* fdesc, const long* ftab, const long* seg, const uint8_t* huff, int nhuff, int B,
+                                          long nseg, int16_t* coef, long coef_blocks, int* status, hipStream_t stream)
+{
+    if (!bytes || !fdesc_host || !ftab_host || !seg_host || !fdesc || !ftab || !seg || !huff || !coef || !status)
+        return (int)hipErrorInvalidValue;
+    // the kernel stages 16 bytes per lane: the byte buffer is 16-byte aligned and a whole number of such pieces
+    if (((uintptr_t)bytes & 15) || (nbytes & 15) || ((uintptr_t)coef & 15)) return (int)hipErrorInvalidValue;
+    if (!check_entropy_tables(nbytes, fdesc_host, ftab_host, seg_host, nhuff, B, nseg, coef_blocks)) return (int)hipErrorInvalidValue;
+    if (nseg > 0x7fffffffL) return (int)hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(status, 0, (size_t)B * sizeof(int), stream);
+    if (e != hipSuccess) return (int)e;
+    if (nseg == 0) return 0;
+    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)nseg), dim3(EDITOR_WAVE), 0, stream, bytes, nbytes, fdesc, ftab, seg, huff, B, nseg,
+                       coef, status);
     EDITOR_LAUNCH_CHECK();
     return 0;
 }

@@ -388,6 +388,17 @@ class DeviceTrainTransform:
         return out
 
 
+class JpegBatchPlan:
+    """What DeviceJpegDecoder.plan_batch learns about a batch without decoding it (editor_jpeg_plan, include/editor_hip.h):
+    infos (B,16) int32, plans (B,16) int32 (plans[:,0]: device-eligible), qts (B,192) uint16, huffs (B,8,272) uint8, and
+    segs (nseg,3) int64 - the restart segments of the ELIGIBLE files, file after file."""
+
+    def __init__(self, b):
+        self.infos, self.plans = np.zeros((b, 16), dtype=np.int32), np.zeros((b, 16), dtype=np.int32)
+        self.qts, self.huffs = np.zeros((b, 192), dtype=np.uint16), np.zeros((b, 8, 272), dtype=np.uint8)
+        self.segs, self.nseg = np.zeros((max(64, 4 * b), 3), dtype=np.int64), 0
+
+
 class DeviceJpegDecoder:
     """`Image.open(path).convert('RGB')` + the 256-wide crops of data/datasets/bases.py:9-41 for a BATCH of baseline JPEG
     files: the host Huffman-decodes each file into quantised DCT coefficients (a thread pool; the C entry point releases
@@ -404,11 +415,24 @@ class DeviceJpegDecoder:
     refusing such a batch.
 
     Baseline, extended-sequential and progressive Huffman files (round 4) are covered; arithmetic-coded / lossless / 12-bit /
-    4-component files raise (EDITOR_JPEG_UNSUPPORTED) and an incomplete progressive file is corrupt: no silent host fallback."""
+    4-component files raise (EDITOR_JPEG_UNSUPPORTED) and an incomplete progressive file is corrupt: no silent host fallback.
 
-    def __init__(self, crop_w=256, threads=8):
+    entropy="device" moves the Huffman decode of ordinary baseline files to the GPU, for __call__ and decode_ragged alike: the
+    host plans each file (editor_jpeg_plan: one pass over its bytes), the compressed scan bytes are uploaded instead of int16
+    blocks, and editor_jpeg_entropy_device - one wave per restart segment of the batch - writes the same coefficient planes, bit
+    for bit; reconstruction is unchanged.  Device-eligible: SOF0 / SOF1, exactly one SOS naming every component in frame order,
+    restart markers (if an interval is defined) all present and in order.  Every other file the parser accepts (progressive,
+    several scans, irregular restarts) is decoded on the host as before and its coefficients copied in - a documented routing
+    rule.  Same errors, same text; the one difference: corrupt ENTROPY data is found after the launch (the status
+    vector is read back before the call returns), not before it."""
+
+    def __init__(self, crop_w=256, threads=8, entropy="host"):
         from concurrent.futures import ThreadPoolExecutor
         from . import _lib
+        if entropy not in ("host", "device"):
+            raise ValueError("DeviceJpegDecoder: entropy is 'host' or 'device'")
+        self.entropy = entropy
+        self.last_h2d_bytes = 0                              # bytes the last call copied to the device (tools/ragged_input_time.py)
         self.crop_w = int(crop_w)
         self._cd = _lib.lib().cdll
         self._pool = ThreadPoolExecutor(max_workers=max(1, int(threads)))
@@ -438,10 +462,196 @@ class DeviceJpegDecoder:
         if rc:
             raise ValueError("JPEG entropy decode failed (rc %d)" % rc)
 
+    # ---- entropy="device": the scans are Huffman-decoded by editor_jpeg_entropy_device -------------------------------------
+    def plan_batch(self, files):
+        """editor_jpeg_plan over a batch, on the calling thread (one pass over each file's bytes).  -> JpegBatchPlan; raises
+        ValueError naming the file's index for a file editor_jpeg_parse refuses, before anything is launched."""
+        b = len(files)
+        bp = JpegBatchPlan(b)
+        used = 0
+        fn = self._cd.editor_jpeg_plan
+        p_info, p_plan, p_qt, p_huff = (a.ctypes.data for a in (bp.infos, bp.plans, bp.qts, bp.huffs))
+        for i, f in enumerate(files):
+            buf = np.frombuffer(f, dtype=np.uint8)
+            while True:
+                cap = bp.segs.shape[0] - used
+                rc = fn(ctypes.c_void_p(buf.ctypes.data), len(f), ctypes.c_void_p(p_info + 64 * i), ctypes.c_void_p(p_plan + 64 * i),
+                        ctypes.c_void_p(p_qt + 384 * i), ctypes.c_void_p(p_huff + 2176 * i), ctypes.c_void_p(bp.segs.ctypes.data + 24 * used), cap)
+                if rc:
+                    raise ValueError("file %d of the batch: %s" % (i, self._refusal(rc)))
+                ns = int(bp.plans[i, 1])
+                if not bp.plans[i, 0] or ns <= cap:
+                    break
+                bp.segs = np.concatenate([bp.segs, np.zeros((max(bp.segs.shape[0], ns), 3), dtype=np.int64)])
+            if bp.plans[i, 0]:                                # (a host-routed file's rows are overwritten by the next file's)
+                used += ns
+        bp.nseg = used
+        return bp
+
+    def pack_batch(self, files, bp, block_off):
+        """The tables editor_jpeg_entropy_segments / _device take for a planned batch (include/editor_hip.h), host arrays:
+        -> (nbytes, spans, fdesc, ftab, segs, huff, nseg).  spans: (file index, position in the byte buffer, first scan byte,
+        end of the scan bytes) per eligible file - only those bytes travel, each file's at a multiple of 16."""
+        b = len(files)
+        elig = bp.plans[:, 0] != 0
+        nsegs = np.where(elig, bp.plans[:, 1], 0).astype(np.int64)
+        segpref = np.cumsum(nsegs)
+        nseg = int(segpref[-1])
+        assert nseg == bp.nseg
+        segs = bp.segs[:max(nseg, 1)]
+        e_idx = np.nonzero(elig)[0]
+        s0 = segs[(segpref - nsegs)[e_idx], 0]
+        e1 = segs[segpref[e_idx] - 1, 1]
+        padded = (e1 - s0 + 15) & ~15
+        pos = np.cumsum(padded) - padded
+        nbytes = max(int(padded.sum()), 16)
+        byte_off = np.zeros(b, dtype=np.int64)
+        byte_off[e_idx] = pos - s0
+        ftab = np.stack([np.asarray(block_off, dtype=np.int64), byte_off, segpref]).astype(np.int64)
+        fdesc = np.zeros((b, 16), dtype=np.int32)
+        fdesc[:, 0:5] = bp.infos[:, 2:7]
+        fdesc[:, 5] = bp.plans[:, 2]
+        pool, rows, memo = [], {}, {}
+        for i in e_idx.tolist():                              # the batch's pool of distinct Huffman tables
+            key = (bp.huffs[i].tobytes(), bp.plans[i, 4:10].tobytes())
+            slots = memo.get(key)
+            if slots is None:
+                slots = []
+                for c in range(3):
+                    for sel in (int(bp.plans[i, 4 + c]), 4 + int(bp.plans[i, 7 + c])):
+                        t = bp.huffs[i, sel].tobytes()
+                        if t not in rows:
+                            rows[t] = len(pool)
+                            pool.append(bp.huffs[i, sel])
+                        slots.append(rows[t])
+                slots = memo[key] = slots[0::2] + slots[1::2]
+            fdesc[i, 6:12] = slots
+        huff = np.stack(pool) if pool else np.zeros((1, 272), dtype=np.uint8)
+        spans = list(zip(e_idx.tolist(), pos.tolist(), s0.tolist(), e1.tolist()))
+        return nbytes, spans, fdesc, ftab, segs, huff, nseg
+
+    def _device_entropy(self, files, bp, coef_d, block_off, device, extra=()):
+        """Fills coef_d (flat int16 device tensor) at block_off[i] for every file of the planned batch: ONE host-to-device copy
+        of the eligible files' scan bytes + descriptor tables (+ the caller's `extra` arrays) and one launch of
+        editor_jpeg_entropy_device; a host-routed file is decoded by editor_jpeg_entropy_decode on the pool and its range copied
+        (one copy per such file).  -> (status tensor, device views of extra)."""
+        b = len(files)
+        nbytes, spans, fdesc, ftab, segs, huff, nseg = self.pack_batch(files, bp, block_off)
+        h_idx = np.nonzero(bp.plans[:, 0] == 0)[0].tolist()
+        parts = [fdesc, ftab, segs, huff] + [np.ascontiguousarray(a) for a in extra]
+        offs, o = [], nbytes
+        for a in parts:
+            offs.append(o)
+            o += (a.nbytes + 15) & ~15
+        blob = o
+        h_off = []
+        for i in h_idx:
+            h_off.append(o)
+            o += int(bp.infos[i, 8]) * 128
+        arena = self._stage(o)
+        host = arena.numpy()
+        for i, at, s0, e1 in spans:
+            host[at:at + e1 - s0] = np.frombuffer(files[i], dtype=np.uint8)[s0:e1]
+        for a, at in zip(parts, offs):
+            host[at:at + a.nbytes] = a.reshape(-1).view(np.uint8)
+        if h_idx:
+            base = arena.data_ptr()
+            sq, si = np.zeros((len(h_idx), 192), dtype=np.uint16), np.zeros((len(h_idx), 16), dtype=np.int32)
+
+            def entropy(j):
+                try:
+                    self._entropy(files[h_idx[j]], base + h_off[j], int(bp.infos[h_idx[j], 8]), sq[j].ctypes.data, si[j])
+                except ValueError as e:
+                    raise ValueError("file %d of the batch: %s" % (h_idx[j], e)) from None
+            list(self._pool.map(entropy, range(len(h_idx))))
+        coef_blocks = coef_d.numel() // 64
+        with torch.cuda.device(device):
+            blob_d = torch.empty(blob, dtype=torch.uint8, device=device)
+            blob_d.copy_(arena[:blob], non_blocking=True)
+            for j, i in enumerate(h_idx):
+                n16 = int(bp.infos[i, 8]) * 64
+                coef_d[int(block_off[i]) * 64:int(block_off[i]) * 64 + n16].copy_(arena[h_off[j]:h_off[j] + 2 * n16].view(torch.int16), non_blocking=True)
+            self._h2d_done = torch.cuda.Event()
+            self._h2d_done.record()
+            self.last_h2d_bytes = o
+            dev = [blob_d[at:at + a.nbytes] for a, at in zip(parts, offs)]
+            status = torch.empty(b, dtype=torch.int32, device=device)
+            call("editor_jpeg_entropy_device", blob_d[:nbytes], nbytes, ctypes.c_void_p(fdesc.ctypes.data), ctypes.c_void_p(ftab.ctypes.data),
+                 ctypes.c_void_p(segs.ctypes.data), dev[0].view(torch.int32), dev[1].view(torch.int64), dev[2].view(torch.int64), dev[3],
+                 int(huff.shape[0]), b, nseg, coef_d, coef_blocks, status)
+        return status, dev[4:]
+
+    @staticmethod
+    def _raise_status(status):
+        """Reads the kernel's per-file status back (a synchronisation): corrupt entropy data is reported AFTER the launch."""
+        bad = torch.nonzero(status).flatten().tolist()
+        if bad:
+            raise ValueError("file %d of the batch: JPEG entropy decode failed (rc %d)" % (bad[0], int(status[bad[0]])))
+
+    def _call_device(self, files, device):
+        files = list(files)
+        bp = self.plan_batch(files)
+        infos = bp.infos
+        w, h = int(infos[0][0]), int(infos[0][1])
+        cw = self.crop_w if self.crop_w > 0 else w
+        ncrop = w // cw
+        if ncrop < 1 or (infos[:, 0] != w).any() or (infos[:, 1] != h).any():
+            raise ValueError("DeviceJpegDecoder: the files of a batch must share one image size >= the crop width")
+        b = len(files)
+        groups = {}
+        for i, inf in enumerate(infos):                      # one reconstruct call per coefficient geometry; ONE entropy launch
+            groups.setdefault(tuple(int(v) for v in inf[:9]), []).append(i)
+        order = [i for idx in groups.values() for i in idx]
+        block_off = np.zeros(b, dtype=np.int64)
+        blocks = infos[order, 8].astype(np.int64)
+        block_off[order] = np.cumsum(blocks) - blocks        # file j of a group sits at the group's start + j * blocks_per_image
+        total = int(blocks.sum())
+        with torch.cuda.device(device):
+            coef_d = torch.empty(total * 64, dtype=torch.int16, device=device)
+            out = torch.empty(ncrop, b, h, cw, 3, dtype=torch.uint8, device=device)
+        status, (qt_d,) = self._device_entropy(files, bp, coef_d, block_off, device, extra=[bp.qts[order]])
+        qt_d = qt_d.view(torch.int16)
+        at = 0
+        for key, idx in groups.items():
+            n, nb = len(idx), key[8]
+            ginfo = np.ascontiguousarray(infos[idx[0]])
+            pb = ctypes.c_long(0)
+            self._cd.editor_jpeg_planes_bytes(ctypes.c_void_p(ginfo.ctypes.data), ctypes.byref(pb))
+            planes = torch.empty(n * pb.value, dtype=torch.uint8, device=device)
+            dst = out if n == b else torch.empty(ncrop, n, h, cw, 3, dtype=torch.uint8, device=device)
+            first = int(block_off[idx[0]])
+            call("editor_jpeg_reconstruct", coef_d[first * 64:(first + n * nb) * 64], qt_d[at * 192:(at + n) * 192],
+                 ctypes.c_void_p(ginfo.ctypes.data), n, planes, cw, dst)
+            if n != b:
+                out[:, torch.tensor(idx, device=device)] = dst
+            at += n
+        self._raise_status(status)
+        return out
+
+    def _decode_ragged_device(self, files, device):
+        b = len(files)
+        bp = self.plan_batch(files)
+        infos = bp.infos
+        tab, nblocks, npixels = ragged_decode_plan(infos)
+        with torch.cuda.device(device):
+            coef_d = torch.empty(nblocks * 64, dtype=torch.int16, device=device)
+        status, (qt_d, info_d, tab_d) = self._device_entropy(files, bp, coef_d, tab[0], device, extra=[bp.qts, infos, tab])
+        with torch.cuda.device(device):
+            planes = torch.empty(nblocks * 64, dtype=torch.uint8, device=device)
+            data = torch.empty(npixels * 3, dtype=torch.uint8, device=device)
+            call("editor_jpeg_reconstruct_ragged", coef_d, qt_d.view(torch.int16), ctypes.c_void_p(infos.ctypes.data), ctypes.c_void_p(tab.ctypes.data),
+                 info_d.view(torch.int32), tab_d.view(torch.int64), b, planes, data)
+        self._raise_status(status)
+        offsets = np.concatenate([tab[2], [npixels * 3]]).astype(np.int64)
+        sizes = np.ascontiguousarray(infos[:, [1, 0]])
+        return RaggedImages(data, torch.from_numpy(offsets), torch.from_numpy(sizes))
+
     def __call__(self, files, device):
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("DeviceJpegDecoder reconstructs on the GPU (no CPU fallback)")
+        if self.entropy == "device":
+            return self._call_device(files, device)
         infos = [self.parse(f) for f in files]
         w, h = int(infos[0][0]), int(infos[0][1])
         cw = self.crop_w if self.crop_w > 0 else w
@@ -485,7 +695,8 @@ class DeviceJpegDecoder:
         (grayscale replicated to three channels, as `convert('RGB')` does).  Every file is parsed before anything is launched: a
         corrupt or unsupported one raises ValueError naming its index in the batch.  Then the thread pool Huffman-decodes each
         file into the staging buffer at the file's block offset, three host-to-device copies (coefficients, quantisation tables,
-        descriptor table) and ONE call of the ragged entry: two launches per batch, whatever the sizes."""
+        descriptor table) and ONE call of the ragged entry: two launches per batch, whatever the sizes.  With entropy="device"
+        (class docstring) the files are planned instead, one copy carries scan bytes and tables, and a third launch decodes them."""
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("DeviceJpegDecoder reconstructs on the GPU (no CPU fallback)")
@@ -493,6 +704,8 @@ class DeviceJpegDecoder:
         b = len(files)
         if b < 1:
             raise ValueError("DeviceJpegDecoder.decode_ragged: empty batch")
+        if self.entropy == "device":
+            return self._decode_ragged_device(files, device)
         infos = np.zeros((b, 16), dtype=np.int32)
         for i, rc in enumerate(self._pool.map(lambda i: self._parse_rc(files[i], infos[i]), range(b))):
             if rc:
@@ -522,6 +735,7 @@ class DeviceJpegDecoder:
             desc_d.copy_(arena[n_coef + n_qt:o_tab + tab.nbytes], non_blocking=True)
             self._h2d_done = torch.cuda.Event()
             self._h2d_done.record()
+            self.last_h2d_bytes = o_tab + tab.nbytes
             planes = torch.empty(nblocks * 64, dtype=torch.uint8, device=device)
             data = torch.empty(npixels * 3, dtype=torch.uint8, device=device)
             call("editor_jpeg_reconstruct_ragged", coef_d, qt_d, ctypes.c_void_p(infos.ctypes.data), ctypes.c_void_p(tab.ctypes.data),
@@ -534,10 +748,11 @@ class DeviceJpegDecoder:
 _DEFAULT = {}
 
 
-def load_modalities(files_by_modality, size, interpolation=3, device="cuda"):
+def load_modalities(files_by_modality, size, interpolation=3, device="cuda", entropy="host"):
     """The separate-file sample layout (RGBNT201 / MSVR310: img_path is a list of one path per modality, each file resized on
     its own, data/datasets/bases.py:22-30).  files_by_modality: nmod lists of B byte strings -> nmod uint8 (B,Hout,Wout,3)
-    tensors in the order given: ONE ragged decode + ONE ragged resize over all nmod * B files."""
+    tensors in the order given: ONE ragged decode + ONE ragged resize over all nmod * B files.  entropy: where the Huffman
+    decode runs, as DeviceJpegDecoder's keyword ("host", the default, or "device")."""
     if torch.device(device).type != "cuda":
         raise RuntimeError("load_modalities decodes on the GPU (no CPU fallback)")
     groups = [list(g) for g in files_by_modality]
@@ -546,9 +761,10 @@ def load_modalities(files_by_modality, size, interpolation=3, device="cuda"):
     b = len(groups[0])
     if any(len(g) != b for g in groups):
         raise ValueError("load_modalities: every modality lists the same number of files")
-    dec = _DEFAULT.get("decoder")
+    dkey = "decoder" if entropy == "host" else ("decoder", entropy)
+    dec = _DEFAULT.get(dkey)
     if dec is None:
-        dec = _DEFAULT["decoder"] = DeviceJpegDecoder(crop_w=0, threads=16)
+        dec = _DEFAULT[dkey] = DeviceJpegDecoder(crop_w=0, threads=16, entropy=entropy)
     key = (int(size[0]), int(size[1]), int(interpolation))
     rs = _DEFAULT.get(key)
     if rs is None:

@@ -514,6 +514,39 @@ int editor_jpeg_reconstruct(const int16_t* coef, const uint16_t* qt, const int* 
 int editor_jpeg_reconstruct_ragged(const int16_t* coef, const uint16_t* qt, const int* info_host, const long* tab_host,
                                    const int* info, const long* tab, int B, uint8_t* planes, uint8_t* out,
                                    editor_stream_t stream);
+/* ---- Huffman decode of sequential scans ON THE DEVICE (DeviceJpegDecoder(entropy="device")) ----
+ * A file is DEVICE-ELIGIBLE when: the frame is SOF0 / SOF1; it has exactly ONE SOS, which names every component of the frame
+ * in frame order (the interleaved scan libjpeg writes, or the lone component of a grayscale file) with tables that are
+ * defined; and, with a restart interval Ri, its entropy-coded bytes hold exactly ceil(nMCU / Ri) - 1 RSTn markers cycling
+ * D0..D7 (none without one).  Every other file editor_jpeg_parse accepts keeps going through editor_jpeg_entropy_decode.
+ * HOST planner, one pass over the file's bytes, no bit-level work.  Return value and info as editor_jpeg_parse.
+ *   plan (16 ints): eligible, segments of the first scan (= RSTn markers met + 1), restart interval, MCUs, DC table selector
+ *        of component 0..2, AC table selector of 0..2, number of SOS markers, 0...
+ *   qt   (3 x 64 uint16) as editor_jpeg_entropy_decode returns it
+ *   huff (8 x 272 bytes): DC tables 0..3 then AC tables 0..3 as they stand at the scan header, each in its DHT form (16 length
+ *        counts, then the values); tables the scan does not name are zero.  They have passed the decoder's code-space check.
+ *   seg  (seg_cap x 3 int64): [byte start, byte end) of the entropy-coded bytes between restart markers (markers excluded;
+ *        the last ends at the next other marker or at n) and the segment's first MCU, k * Ri.  At most seg_cap rows are
+ *        written; plan[1] is the count either way. */
+int editor_jpeg_plan(const uint8_t* data, long n, int* info, int* plan, uint16_t* qt, uint8_t* huff, long* seg, long seg_cap);
+/* The segment decoder over a planned BATCH.  bytes: the files' scan bytes packed in one buffer of nbytes.
+ *   fdesc (B,16) int32: ncomp, hmax, vmax, mcus_x, mcus_y, restart interval, row in `huff` of the DC table of component 0..2,
+ *         of the AC table of component 0..2, 0...;  huff: nhuff x 272 bytes, the batch's pool of DHT-form tables
+ *   ftab  (3,B) int64: first coefficient block of file i in coef; where byte 0 of file i would sit in `bytes` (only the scan's
+ *         bytes need be present, so this may be negative); INCLUSIVE prefix sum of segments (a file decoded elsewhere: none)
+ *   seg   (nseg,3) int64: editor_jpeg_plan's rows, file after file
+ * Every block of a listed file's range in coef is written (zero where the scan says so); status[i] = 0 or EDITOR_JPEG_CORRUPT
+ * (code not found, DC size above 11, coefficient index past 63).  hipErrorInvalidValue when the tables do not describe
+ * in-range segments that cover every MCU of their file once.
+ * HOST twin: all pointers host memory; the same routine the kernel runs. */
+int editor_jpeg_entropy_segments(const uint8_t* bytes, long nbytes, const int* fdesc, const long* ftab, const long* seg,
+                                 const uint8_t* huff, int nhuff, int B, long nseg, int16_t* coef, long coef_blocks, int* status);
+/* DEVICE: one wave per segment of the batch.  The tables twice: *_host to validate, the rest (and bytes, huff, coef, status)
+ * in device memory; bytes and coef 16-byte aligned, nbytes a multiple of 16.  status is written on the stream. */
+int editor_jpeg_entropy_device(const uint8_t* bytes, long nbytes, const int* fdesc_host, const long* ftab_host,
+                               const long* seg_host, const int* fdesc, const long* ftab, const long* seg, const uint8_t* huff,
+                               int nhuff, int B, long nseg, int16_t* coef, long coef_blocks, int* status,
+                               editor_stream_t stream);
 
 /* T.Resize(size, interpolation) of decoded uint8 images (make_dataloader.py:246,256; torchvision 0.14.1 ->
  * PIL.Image.resize = Pillow ImagingResample, 8-bit path): horizontal pass then vertical pass with 22-bit fixed-point taps.

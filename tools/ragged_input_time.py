@@ -4,7 +4,10 @@ drawn from a seeded spread (about 60x130 to 160x340), resized to 256x128 bicubic
     (a) the host stage alone: parse + Huffman decode of every file on 16 threads (no device work)
     (b) DeviceJpegDecoder.decode_ragged + DeviceResize on the RaggedImages, end to end (host clock, ends in a synchronise)
     (c) the yardstick: DeviceJpegDecoder.__call__ + DeviceResize on 384 files of ONE size with the same total pixel count
-and (b) against the 9 400 files/s the benchmarked tri-modal step consumes (about 3 100 img/s x 3 files).
+    (d) the planner alone: editor_jpeg_plan of every file on the calling thread (what entropy="device" leaves on the host)
+    (e) the same as (b) with DeviceJpegDecoder(entropy="device"): the scans are Huffman-decoded by editor_jpeg_entropy_device
+and (b) against the 9 400 files/s the benchmarked tri-modal step consumes (about 3 100 img/s x 3 files); the host-to-device bytes
+per batch of (b) and (e); the entropy kernel alone (stream time, inputs already on the device).  (b) is the yardstick for (e).
     python tools/ragged_input_time.py [--reps 10]"""
 import argparse
 import ctypes
@@ -98,11 +101,54 @@ def main():
 
     out = run_ragged()
     assert tuple(out.shape) == (n,) + SIZE + (3,)
+    h2d_b = dec.last_h2d_bytes
+
+    # (d) the planner alone, (e) entropy="device" end to end, between two more runs of (b)
+    dev = DeviceJpegDecoder(crop_w=0, threads=16, entropy="device")
+    t_d = wall(lambda: dev.plan_batch(ragged), a.reps)
+
+    def run_device():
+        return rs(dev.decode_ragged(ragged, "cuda"))
+    assert torch.equal(run_device(), out)
+    h2d_e = dev.last_h2d_bytes
+    t_e = wall(run_device, a.reps)
+    t_b3 = wall(run_ragged, a.reps)
+    t_e2 = wall(run_device, a.reps)
+    # the entropy kernel alone
+    from editor_amd._lib import call
+    bp = dev.plan_batch(ragged)
+    tab = np.concatenate([[0], np.cumsum(bp.infos[:, 8].astype(np.int64))])
+    nbytes, spans, fdesc, ftab, segs, huff, nseg = dev.pack_batch(ragged, bp, tab[:-1])
+    buf = np.zeros(nbytes, dtype=np.uint8)
+    for i, at, lo, hi in spans:
+        buf[at:at + hi - lo] = np.frombuffer(ragged[i], dtype=np.uint8)[lo:hi]
+    d = [torch.from_numpy(x).cuda() for x in (buf, fdesc, ftab, segs, huff)]
+    coef_d = torch.empty(int(tab[-1]) * 64, dtype=torch.int16, device="cuda")
+    status = torch.empty(n, dtype=torch.int32, device="cuda")
+
+    def kernel():
+        call("editor_jpeg_entropy_device", d[0], nbytes, ctypes.c_void_p(fdesc.ctypes.data), ctypes.c_void_p(ftab.ctypes.data),
+             ctypes.c_void_p(segs.ctypes.data), d[1], d[2], d[3], d[4], int(huff.shape[0]), n, nseg, coef_d, int(tab[-1]), status)
+    kernel()
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(a.reps):
+        kernel()
+    e1.record()
+    torch.cuda.synchronize()
+    t_k = e0.elapsed_time(e1) / a.reps / 1e3
+    assert not status.any() and np.array_equal(coef_d.cpu().numpy().reshape(-1, 64), coef)      # (a)'s host coefficients
     for name, t in (("(a) host parse + Huffman, 16 threads", t_a), ("(b) ragged decode + resize, end to end", t_b),
                     ("(b) again", t_b2), ("(c) uniform decode + resize, end to end", t_c)):
         print("%-44s %8.2f ms / batch  %9.0f files/s" % (name, 1e3 * t, n / t))
     print("%-44s %8.2f ms / batch  (host table building + 2 launches, stream time)" % ("    ragged resize alone", 1e3 * t_rs))
-    best_b = min(t_b, t_b2)
+    for name, t in (("(b) once more, after (e)", t_b3), ("(d) planner alone, one thread", t_d), ("(e) entropy=device decode + resize, end to end", t_e),
+                    ("(e) again", t_e2)):
+        print("%-44s %8.2f ms / batch  %9.0f files/s" % (name, 1e3 * t, n / t))
+    print("%-44s %8.2f ms / batch  (%d segments, one wave each, stream time)" % ("    entropy kernel alone", 1e3 * t_k, nseg))
+    print("host-to-device bytes per batch: (b) %.2f MB   (e) %.2f MB" % (h2d_b / 1e6, h2d_e / 1e6))
+    best_b, best_e = min(t_b, t_b2, t_b3), min(t_e, t_e2)
+    print("(e) / (b): x %.2f of (b)'s time  (%.0f against %.0f files/s)" % (best_e / best_b, n / best_e, n / best_b))
     print("(b) / step demand (%.0f files/s): x %.2f   (b) / (c): x %.2f   (a) / (b): x %.2f of (b)'s time is the host stage"
           % (STEP_FILES_PER_S, n / best_b / STEP_FILES_PER_S, t_c / best_b, t_a / best_b))
 

@@ -10,6 +10,9 @@
 //          (editor_jpeg_entropy_device, with its planner editor_jpeg_plan and host twin editor_jpeg_entropy_segments): the
 //          Huffman decode itself for files with one whole-frame sequential scan, one wave per restart segment of the batch, so
 //          such files cross the bus as compressed bytes (DeviceJpegDecoder(entropy="device"); the host decode stays the default).
+//          (editor_jpeg_entropy_split_device, host twin editor_jpeg_entropy_split_segments): the same decode, parallel INSIDE a
+//          segment - 256 lanes per segment, self-synchronising subsequences - for files without restart markers
+//          (DeviceJpegDecoder(entropy="device_split")).
 // The arithmetic restates libjpeg's default decompression path - the one Pillow runs (JDCT_ISLOW, do_fancy_upsampling) -
 // integer for integer, so the pixels are BIT-IDENTICAL to Pillow's (tests/golden/f14_decode.npz):
 //   jidctint.c  jpeg_idct_islow      13-bit constants, two passes, DESCALE rounding, range-limit table
@@ -964,6 +967,358 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
     if (lane == 0 && rc != SEG_DONE) status[f] = EDITOR_JPEG_CORRUPT;
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------
+// the same decode, parallel INSIDE a segment: self-synchronising subsequences (Klein & Wiseman; Weissenberger & Schmidt)
+// ------------------------------------------------------------------------------------------------------------------
+// A segment's bytes [start, end) are cut at start + k * sub_bytes; one lane owns one subsequence: every symbol (a Huffman code
+// and its extra bits) that BEGINS in it.  SPLIT_LANES subsequences make a chunk; one workgroup walks its segment chunk by
+// chunk and carries the exact state from one chunk into the next, so nothing ever waits for another workgroup.  In a chunk:
+//   round 0     lane 0 starts from the carried (exact) state, every other lane guesses (block 0 of an MCU, a DC size next)
+//   round r     a lane whose left neighbour's exit state changed starts again from it; lanes 0..r are exact after round r,
+//               so the loop is bounded by the subsequence count whatever the data - synchronisation only ends it early
+//   then        an exclusive prefix sum of the lanes' completed-block counts names each lane's first block, and one more
+//               walk writes the non-zero AC coefficients and the DC DIFFERENCES of the blocks below the segment's count
+// A truncated segment's remaining blocks come from the zero tail SegReader::fill feeds; lane 0 decodes them, at most 64 symbols a
+// block.  Last, a per-component prefix sum over the segment's blocks in scan order turns the differences into values:
+// (int16_t) of a running sum depends on the sum modulo 2^16 only, so it may be regrouped freely.
+//   bytes    as above: bounded by the segment's end and by the staged window, zeros past either
+//   writes   block index = prefix sum of counts; destination = scan_block(block index) - never from data; below nblk only
+//   loops    a walk: every symbol consumes at least one bit, so at most 8 x sub_bytes symbols (the tail: 64 per block);
+//            rounds: the subsequence count; chunks: the byte length
+enum { SPLIT_LANES = 256, SPLIT_MARGIN = 64, SPLIT_SUB_MIN = 16, SPLIT_SUB_MAX = 128 };
+enum { SUB_ERR = 1, SUB_EXH = 2 };
+// (a symbol is at most 31 bits and the reader runs at most 56 bits ahead: under 22 bytes with every byte stuffed, plus the
+//  15 bytes the window's start is aligned down by - SPLIT_MARGIN bytes staged past a chunk cover every read of its lanes)
+
+inline bool split_sub_ok(int sub) { return sub >= SPLIT_SUB_MIN && sub <= SPLIT_SUB_MAX && (sub & (sub - 1)) == 0; }
+
+// The decoder's state at a point of the stream, in ONE form per point so that equal points compare equal:
+//   p      the byte that holds the next bit (after a stuffed FF 00 pair: the byte after the 00)
+//   s      bit in that byte (0 = its top bit) | block in the MCU << 3 | coefficient index << 6 (0: a DC size is next) | flags << 12
+//          SUB_EXH  the data ended at p (the segment's end, or a marker): only zeros follow, bit is 0
+//          SUB_ERR  absorbing: one of decode()'s three errors happened before this point (p and the rest are 0)
+struct SubState { long p; int s; };
+__host__ __device__ __forceinline__ bool sub_differs(const SubState& a, const SubState& b) { return a.p != b.p || a.s != b.s; }
+
+// SegReader that can say where it is: which loaded bytes took two stream bytes (`stuffed`, newest in bit 0) and how many of
+// the loaded bits are the zeros fed past the data (`vbits`, always the newest).
+struct SubReader {
+    const uint8_t* buf; long base, lim;            // the window, as SegReader's
+    long p, end;
+    uint64_t acc; int nbits, vbits; uint32_t stuffed; bool marker;
+    __host__ __device__ __forceinline__ void fill() {
+        while (nbits <= 24) {
+            if (!marker && p >= base && p + 4 <= end && p + 4 <= lim) {
+                const uint8_t* q = buf + (p - base);
+                const uint32_t b0 = q[0], b1 = q[1], b2 = q[2], b3 = q[3];
+                if (b0 != 0xFF && b1 != 0xFF && b2 != 0xFF && b3 != 0xFF) {
+                    acc = (acc << 32) | ((b0 << 24) | (b1 << 16) | (b2 << 8) | b3);
+                    nbits += 32; p += 4; stuffed <<= 4;
+                    continue;
+                }
+            }
+            uint8_t b = 0;
+            if (!marker && p < end && p >= base && p < lim) {
+                b = buf[p - base];
+                if (b == 0xFF) {
+                    if (p + 1 < end && p + 1 < lim && buf[p + 1 - base] == 0x00) { p += 2; stuffed = (stuffed << 1) | 1u; }
+                    else { marker = true; b = 0; }
+                } else { ++p; stuffed <<= 1; }
+            } else {
+                marker = true;
+            }
+            if (marker && vbits < 64) vbits += 8;                          // (64 or more: everything held is past the data)
+            acc = (acc << 8) | b;
+            nbits += 8;
+        }
+    }
+    __host__ __device__ __forceinline__ int peek(int n) { if (nbits < n) fill(); return (int)((acc >> (nbits - n)) & ((1u << n) - 1)); }
+    __host__ __device__ __forceinline__ void drop(int n) { nbits -= n; }
+    __host__ __device__ __forceinline__ int get(int n) { if (n == 0) return 0; const int v = peek(n); drop(n); return v; }
+    __host__ __device__ __forceinline__ void seek(long at, int bit) {
+        p = at; acc = 0; nbits = 0; vbits = 0; stuffed = 0; marker = false;
+        if (bit) { peek(bit); drop(bit); }
+    }
+    // all data consumed and the reader has met its end (call after fill())
+    __host__ __device__ __forceinline__ bool exhausted() const { return marker && nbits <= vbits; }
+    // the stream position of the next unconsumed bit: the bytes still held are walked back over, a stuffed one counting two
+    __host__ __device__ __forceinline__ void cursor(long& cp, int& cbit) const {
+        const int real = nbits - vbits;
+        if (real <= 0) { cp = p; cbit = 0; return; }
+        const int part = real & 7, cnt = (real + 7) >> 3;                     // (cnt <= 7: at most 56 bits are held)
+        cp = p - cnt - __builtin_popcount(stuffed & ((1u << cnt) - 1u));
+        cbit = part ? 8 - part : 0;
+    }
+};
+
+template <class R>
+__host__ __device__ __forceinline__ int sub_huff(R& br, const HuffLut& t)    // seg_huff, for either reader
+{
+    const int e = t.look[br.peek(9)];
+    if (e) { br.drop(e >> 8); return e & 0xff; }
+    const int code = br.peek(16);
+    for (int l = 10; l <= 16; ++l) {
+        const int c = code >> (16 - l);
+        if (c <= t.maxcode[l]) { br.drop(l); return t.vals[(c + t.valoff[l]) & 0xff]; }
+    }
+    br.drop(16);
+    return -1;
+}
+
+// what a walk reads: the scan's geometry and tables, and the staged window of the stream (as SegReader's buf / base / lim)
+struct SubCtx {
+    const ScanGeom* g; const HuffLut* lut; const uint8_t* zigzag;
+    const uint8_t* buf; long base, lim, end;
+};
+
+// A lane's guess at the state at its boundary `lo`: a block begins there, unless the boundary splits an FF 00 pair.
+__host__ __device__ __forceinline__ SubState sub_guess(const SubCtx& cx, long lo)
+{
+    SubState s = {lo, 0};
+    if (lo - 1 >= cx.base && lo < cx.lim && lo < cx.end && cx.buf[lo - 1 - cx.base] == 0xFF && cx.buf[lo - cx.base] == 0x00) s.p = lo + 1;
+    return s;
+}
+
+// Walks the symbols that begin before byte `hi`, from state s; s becomes the state at the first symbol that does not, and
+// the number of blocks COMPLETED on the way comes back.  At most `budget` symbols.  tail: no `hi` - the walk goes on through
+// the zeros past the data (and starts only from a state that is there).  WRITE: `blk` is the block s is in; coefficients of
+// blocks below nblk are written into `img` (zero-filled; the DC position gets the DIFFERENCE) and the walk ends at nblk;
+// `bad` is set when one of decode()'s three errors is met in such a block.  Without WRITE an error just ends in SUB_ERR: a
+// lane that guessed wrong has not found corruption.
+template <bool WRITE>
+__host__ __device__ __forceinline__ long sub_walk(SubState& s, const SubCtx& cx, long hi, bool tail, bool exact, long budget, int16_t* img, long m0,
+                                                 long blk, long nblk, bool& bad)
+{
+    bad = false;
+    const int flags = s.s >> 12;
+    if ((flags & SUB_ERR) || ((flags & SUB_EXH) && !tail)) return 0;
+    const ScanGeom& g = *cx.g;
+    SubReader br;
+    br.buf = cx.buf; br.base = cx.base; br.lim = cx.lim; br.end = cx.end;
+    br.seek(s.p, s.s & 7);
+    int w = (s.s >> 3) & 7, k = (s.s >> 6) & 63;
+    long done = 0;
+    int16_t* out = nullptr;
+    bool fresh = true;
+    for (long it = 0; it < budget; ++it) {
+        if (WRITE && blk >= nblk) break;
+        if (br.nbits <= 24) br.fill();
+        if (!tail) {
+            if (br.exhausted()) break;
+            if (br.p >= hi) {                                             // (the cursor is never past br.p)
+                long cp; int cb;
+                br.cursor(cp, cb);
+                if (cp >= hi) break;
+            }
+        }
+        const int c = w < g.hv ? 0 : 1 + w - g.hv;
+        if (WRITE && fresh) {
+            int cc;
+            const long dst = scan_block(g, m0, blk, cc);
+            if (dst < 0 || dst >= g.total_blocks) { bad = true; s.p = 0; s.s = SUB_ERR << 12; return done; }   // (cannot happen: see scan_block)
+            out = img + dst * 64;
+            fresh = false;
+        }
+        if (k == 0) {
+            const int sdc = sub_huff(br, cx.lut[c]);
+            if (sdc < 0 || sdc > 11) { bad = true; if (exact) { s.p = 0; s.s = SUB_ERR << 12; return done; } k = 0; w = 0; continue; }
+            const int diff = sdc ? seg_extend(br.get(sdc), sdc) : 0;
+            if (WRITE) out[0] = (int16_t)diff;
+            k = 1;
+        } else {
+            const int rs = sub_huff(br, cx.lut[3 + c]);
+            if (rs < 0) { bad = true; if (exact) { s.p = 0; s.s = SUB_ERR << 12; return done; } k = 0; w = 0; continue; }
+            const int r = rs >> 4, sz = rs & 15;
+            if (sz == 0) {
+                k = r == 15 ? k + 16 : 64;
+            } else {
+                k += r;
+                if (k > 63) { bad = true; if (exact) { s.p = 0; s.s = SUB_ERR << 12; return done; } k = 0; w = 0; continue; }
+                const int v = seg_extend(br.get(sz), sz);
+                if (WRITE) out[cx.zigzag[k]] = (int16_t)v;                 // (k <= 63 checked above)
+                ++k;
+            }
+        }
+        if (k >= 64) { k = 0; w = w + 1 == g.bpm ? 0 : w + 1; ++done; ++blk; fresh = true; }
+    }
+    long cp; int cb;
+    br.cursor(cp, cb);
+    s.p = cp; s.s = cb | (w << 3) | (k << 6) | (br.exhausted() ? SUB_EXH << 12 : 0);
+    return done;
+}
+
+// the DC differences of blocks [b0, b1) of a segment (scan order), summed per component modulo 2^32 ...
+__host__ __device__ __forceinline__ void dc_lane_sum(const ScanGeom& g, const int16_t* img, long m0, long b0, long b1, uint32_t* sum)
+{
+    for (long b = b0; b < b1; ++b) {
+        int c;
+        const long dst = scan_block(g, m0, b, c);
+        sum[c] += (uint32_t)(int)img[dst * 64];
+    }
+}
+// ... and replaced by the values, pred[c] being the sum over the segment's blocks before b0
+__host__ __device__ __forceinline__ void dc_lane_apply(const ScanGeom& g, int16_t* img, long m0, long b0, long b1, uint32_t* pred)
+{
+    for (long b = b0; b < b1; ++b) {
+        int c;
+        const long dst = scan_block(g, m0, b, c);
+        pred[c] += (uint32_t)(int)img[dst * 64];
+        img[dst * 64] = (int16_t)(uint16_t)pred[c];
+    }
+}
+
+// exclusive prefix sum of one value per lane over the workgroup (tmp: 2 x SPLIT_LANES); every lane calls it
+__device__ __forceinline__ uint32_t split_scan(uint32_t v, uint32_t* tmp, int lane)
+{
+    int cur = 0;
+    tmp[lane] = v;
+    __syncthreads();
+    for (int d = 1; d < SPLIT_LANES; d <<= 1) {
+        uint32_t x = tmp[cur * SPLIT_LANES + lane];
+        if (lane >= d) x += tmp[cur * SPLIT_LANES + lane - d];
+        cur ^= 1;
+        tmp[cur * SPLIT_LANES + lane] = x;
+        __syncthreads();
+    }
+    const uint32_t incl = tmp[cur * SPLIT_LANES + lane];
+    __syncthreads();
+    return incl - v;
+}
+
+// dynamic LDS of jpeg_entropy_split_kernel: the window, then (every offset a multiple of 16) the tables and the lanes' states
+__host__ __device__ inline long split_window_bytes(int sub_bytes) { return (long)SPLIT_LANES * sub_bytes + SPLIT_MARGIN; }
+enum { SPLIT_LDS_FIXED = 6 * (int)sizeof(HuffLut) + SPLIT_LANES * 8 + SPLIT_LANES * 4 + 2 * SPLIT_LANES * 4 + 64 + 32 };
+static_assert(sizeof(HuffLut) % 16 == 0, "the carve below keeps 16-byte offsets");
+
+// one SPLIT_LANES-thread workgroup per restart segment of the whole batch; stats (nseg,2): rounds run, chunks walked
+__global__ __launch_bounds__(SPLIT_LANES) void jpeg_entropy_split_kernel(const uint8_t* __restrict__ bytes, long nbytes, const int* __restrict__ fdesc,
+                                                                         const long* __restrict__ ftab, const long* __restrict__ seg,
+                                                                         const uint8_t* __restrict__ huff, int B, long nseg, int sub_bytes,
+                                                                         int16_t* __restrict__ coef, int* __restrict__ status, long* __restrict__ stats)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t split_lds[];
+    const long wbytes = split_window_bytes(sub_bytes);
+    uint8_t* win = split_lds;
+    HuffLut* lut = reinterpret_cast<HuffLut*>(split_lds + wbytes);
+    long* sh_p = reinterpret_cast<long*>(lut + 6);
+    int* sh_s = reinterpret_cast<int*>(sh_p + SPLIT_LANES);
+    uint32_t* sh_scan = reinterpret_cast<uint32_t*>(sh_s + SPLIT_LANES);
+    uint8_t* zigzag = reinterpret_cast<uint8_t*>(sh_scan + 2 * SPLIT_LANES);
+    long* sh_car = reinterpret_cast<long*>(zigzag + 64);                  // carried: p, s, blocks done
+    const long s = blockIdx.x;
+    if (s >= nseg) return;
+    const int lane = threadIdx.x;
+    const int f = ragged_find(ftab + (long)FT_SEGS * B, B, s);
+    const int* fd = fdesc + (long)f * 16;
+    ScanGeom g;
+    if (!make_scan_geom(fd, g)) return;                                   // (validated on the host before the launch)
+    const long m0 = seg[s * 3 + 2];
+    const long m1 = g.restart && m0 + g.restart < g.nmcu ? m0 + g.restart : g.nmcu;
+    const long nblk = (m1 - m0) * g.bpm;
+    const long bo = ftab[(long)FT_BYTE * B + f];
+    const long start = bo + seg[s * 3], end = bo + seg[s * 3 + 1];        // in `bytes`
+    int16_t* img = coef + ftab[(long)FT_COEF * B + f] * 64;
+
+    if (lane < 64) zigzag[lane] = kZigzagDev[lane];
+    const bool mine = lane < 6 && lane % 3 < g.ncomp;
+    if (mine) lut_lengths(lut[lane], huff + (long)fd[6 + lane] * DHT_BYTES);
+    __syncthreads();
+    for (int t = 0; t < 6; ++t)
+        if (t % 3 < g.ncomp) lut_fill(lut[t], huff + (long)fd[6 + t] * DHT_BYTES, lane, SPLIT_LANES);
+    for (long i = lane; i < nblk * 8; i += SPLIT_LANES) {                 // zero the segment's blocks, 16 bytes per lane
+        int c;
+        const long dst = scan_block(g, m0, i >> 3, c);
+        *reinterpret_cast<uint4*>(img + dst * 64 + (i & 7) * 8) = make_uint4(0, 0, 0, 0);
+    }
+    __threadfence_block();
+    __syncthreads();
+
+    SubCtx cx;
+    cx.g = &g; cx.lut = lut; cx.zigzag = zigzag; cx.buf = win; cx.end = end;
+    const long chunk_bytes = (long)SPLIT_LANES * sub_bytes;
+    const long nchunks = (end - start + chunk_bytes - 1) / chunk_bytes;
+    const long budget = 8L * sub_bytes + 8;
+    SubState car = {start, 0};                                            // (uniform: every lane holds the same copy)
+    long base_blk = 0, rounds = 0, chunks = 0;
+    for (long ch = 0; ch < nchunks; ++ch) {
+        if ((car.s >> 12) || base_blk >= nblk) break;                     // an error, the data's end or the last block: nothing left to find
+        const long c0 = start + ch * chunk_bytes;
+        const long c1 = c0 + chunk_bytes < end ? c0 + chunk_bytes : end;
+        const long wpos = c0 & ~15L;
+        const long need = c1 - wpos + SPLIT_MARGIN - 16 < wbytes ? c1 - wpos + SPLIT_MARGIN - 16 : wbytes;
+        for (long i = (long)lane * 16; i < need; i += SPLIT_LANES * 16) {
+            const long a = wpos + i;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (a >= 0 && a + 16 <= nbytes) v = *reinterpret_cast<const uint4*>(bytes + a);
+            *reinterpret_cast<uint4*>(win + i) = v;
+        }
+        __syncthreads();
+        cx.base = wpos;
+        cx.lim = wpos + ((need + 15) & ~15L) < nbytes ? wpos + ((need + 15) & ~15L) : nbytes;
+        const long nsub = (c1 - c0 + sub_bytes - 1) / sub_bytes;
+        const bool active = lane < nsub;
+        const long lo = c0 + (long)lane * sub_bytes;
+        const long hi = lo + sub_bytes < end ? lo + sub_bytes : end;
+        // `hit`: this lane's last walk was a guess that met an error and went on (block 0, a DC size next): its exit state is
+        // not what an exact walk from the same entry gives, so the rounds go on until the exact front (lane r in round r) redoes it
+        bool bad = false, hit = false;
+        SubState entry = car, exit;
+        if (lane > 0) entry = sub_guess(cx, lo);
+        exit = entry;
+        long cnt = 0;
+        if (active) { cnt = sub_walk<false>(exit, cx, hi, false, lane == 0, budget, img, m0, 0, nblk, bad); hit = bad && lane > 0; }
+        sh_p[lane] = exit.p; sh_s[lane] = exit.s;
+        __syncthreads();
+        ++rounds;
+        for (long r = 1; r < nsub; ++r) {
+            SubState ne = entry;
+            if (active && lane > 0) { ne.p = sh_p[lane - 1]; ne.s = sh_s[lane - 1]; }
+            const bool changed = sub_differs(ne, entry) || (hit && lane <= r);
+            if (!__syncthreads_or(changed || hit)) break;                 // (every neighbour is read before any is rewritten)
+            if (changed) {
+                entry = exit = ne;
+                cnt = sub_walk<false>(exit, cx, hi, false, lane <= r, budget, img, m0, 0, nblk, bad);
+                hit = bad && lane > r;
+                sh_p[lane] = exit.p; sh_s[lane] = exit.s;
+            }
+            __syncthreads();
+            ++rounds;
+        }
+        const long first = base_blk + split_scan(active ? (uint32_t)cnt : 0u, sh_scan, lane);
+        if (active) {
+            SubState t = entry;
+            sub_walk<true>(t, cx, hi, false, true, budget, img, m0, first, nblk, bad);
+            if (bad) status[f] = EDITOR_JPEG_CORRUPT;
+        }
+        if (lane == nsub - 1) { sh_car[0] = exit.p; sh_car[1] = exit.s; sh_car[2] = first + cnt; }
+        __syncthreads();
+        car.p = sh_car[0]; car.s = (int)sh_car[1]; base_blk = sh_car[2];
+        ++chunks;
+        __syncthreads();
+    }
+    // a segment that ends early: its remaining blocks from the zeros past the data
+    if (lane == 0 && !((car.s >> 12) & SUB_ERR) && base_blk < nblk) {
+        SubCtx tc = cx;
+        tc.base = 0; tc.lim = 0;                                          // (no byte is read)
+        SubState t = {car.p, car.s & ~7};
+        bool bad = false;
+        sub_walk<true>(t, tc, 0, true, true, (nblk - base_blk) * 64 + 64, img, m0, base_blk, nblk, bad);
+        if (bad) status[f] = EDITOR_JPEG_CORRUPT;
+    }
+    __threadfence_block();
+    __syncthreads();
+    // DC differences -> values
+    const long per = (nblk + SPLIT_LANES - 1) / SPLIT_LANES;
+    const long b0 = lane * per < nblk ? lane * per : nblk;
+    const long b1 = b0 + per < nblk ? b0 + per : nblk;
+    uint32_t sum[3] = {0, 0, 0}, pred[3] = {0, 0, 0};
+    dc_lane_sum(g, img, m0, b0, b1, sum);
+    for (int c = 0; c < g.ncomp; ++c) pred[c] = split_scan(sum[c], sh_scan, lane);
+    dc_lane_apply(g, img, m0, b0, b1, pred);
+    if (lane == 0) { stats[s * 2] = rounds; stats[s * 2 + 1] = chunks; }
+}
+
 }  // namespace
 
 extern "C" int editor_jpeg_parse(const uint8_t* data, long n, int* info)
@@ -1139,6 +1494,151 @@ extern "C" int editor_jpeg_entropy_device(const uint8_t* bytes, long nbytes, con
     if (nseg == 0) return 0;
     hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)nseg), dim3(EDITOR_WAVE), 0, stream, bytes, nbytes, fdesc, ftab, seg, huff, B, nseg,
                        coef, status);
+    EDITOR_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the same, parallel inside a segment (entropy="device_split") -------------------------------------------------------------
+// workspace: (nseg,2) int64 statistics - rounds run and chunks walked per segment, written by either entry - then the host
+// twin's table of lanes (entry p, exit p: int64; entry s, exit s, blocks completed, guess met an error: int32)
+extern "C" int editor_jpeg_entropy_split_workspace(long nseg, int sub_bytes, long* bytes)
+{
+    if (!bytes || nseg < 0 || nseg > 0x7fffffffL || !split_sub_ok(sub_bytes)) return (int)hipErrorInvalidValue;
+    *bytes = nseg * 16 + (long)SPLIT_LANES * 32;
+    return 0;
+}
+
+extern "C" int editor_jpeg_entropy_split_segments(const uint8_t* bytes, long nbytes, const int* fdesc, const long* ftab, const long* seg,
+                                                  const uint8_t* huff, int nhuff, int B, long nseg, int sub_bytes, void* workspace,
+                                                  long workspace_bytes, int16_t* coef, long coef_blocks, int* status)
+{
+    if (!bytes || !fdesc || !ftab || !seg || !huff || !workspace || !coef || !status) return (int)hipErrorInvalidValue;
+    long ws = 0;
+    if (editor_jpeg_entropy_split_workspace(nseg, sub_bytes, &ws) || workspace_bytes < ws || ((uintptr_t)workspace & 7)) return (int)hipErrorInvalidValue;
+    if (!check_entropy_tables(nbytes, fdesc, ftab, seg, nhuff, B, nseg, coef_blocks)) return (int)hipErrorInvalidValue;
+    long* stats = (long*)workspace;
+    long* en_p = stats + nseg * 2;
+    long* ex_p = en_p + SPLIT_LANES;
+    int* en_s = (int*)(ex_p + SPLIT_LANES);
+    int* ex_s = en_s + SPLIT_LANES;
+    int* cnt = ex_s + SPLIT_LANES;
+    int* hit = cnt + SPLIT_LANES;                                       // (see the kernel)
+    HuffLut lut[6];
+    const long chunk_bytes = (long)SPLIT_LANES * sub_bytes, budget = 8L * sub_bytes + 8;
+    long done = 0;
+    for (int f = 0; f < B; ++f) {
+        status[f] = 0;
+        const long upto = ftab[(long)FT_SEGS * B + f];
+        if (upto == done) continue;
+        const int* fd = fdesc + (long)f * 16;
+        ScanGeom g;
+        make_scan_geom(fd, g);
+        for (int t = 0; t < 6; ++t)
+            if (t % 3 < g.ncomp) {
+                const uint8_t* dht = huff + (long)fd[6 + t] * DHT_BYTES;
+                lut_lengths(lut[t], dht);
+                lut_fill(lut[t], dht, 0, 1);
+            }
+        int16_t* img = coef + ftab[(long)FT_COEF * B + f] * 64;
+        memset(img, 0, (size_t)g.total_blocks * 128);
+        const long bo = ftab[(long)FT_BYTE * B + f];
+        for (long s = done; s < upto; ++s) {
+            const long m0 = seg[s * 3 + 2];
+            const long m1 = g.restart && m0 + g.restart < g.nmcu ? m0 + g.restart : g.nmcu;
+            const long nblk = (m1 - m0) * g.bpm;
+            const long start = bo + seg[s * 3], end = bo + seg[s * 3 + 1];
+            SubCtx cx;
+            cx.g = &g; cx.lut = lut; cx.zigzag = kZigzag; cx.buf = bytes; cx.base = 0; cx.lim = nbytes; cx.end = end;
+            const long nchunks = (end - start + chunk_bytes - 1) / chunk_bytes;
+            SubState car = {start, 0};
+            long base_blk = 0, rounds = 0, chunks = 0;
+            bool bad = false;
+            // the kernel's chunk loop, its lanes one after another
+            for (long ch = 0; ch < nchunks; ++ch) {
+                if ((car.s >> 12) || base_blk >= nblk) break;
+                const long c0 = start + ch * chunk_bytes;
+                const long c1 = c0 + chunk_bytes < end ? c0 + chunk_bytes : end;
+                const long nsub = (c1 - c0 + sub_bytes - 1) / sub_bytes;
+                auto hi_of = [&](long lane) { const long lo = c0 + lane * sub_bytes; return lo + sub_bytes < end ? lo + sub_bytes : end; };
+                for (long lane = 0; lane < nsub; ++lane) {
+                    SubState e = lane ? sub_guess(cx, c0 + lane * sub_bytes) : car, x = e;
+                    cnt[lane] = (int)sub_walk<false>(x, cx, hi_of(lane), false, lane == 0, budget, img, m0, 0, nblk, bad);
+                    hit[lane] = bad && lane > 0;
+                    en_p[lane] = e.p; en_s[lane] = e.s; ex_p[lane] = x.p; ex_s[lane] = x.s;
+                }
+                ++rounds;
+                for (long r = 1; r < nsub; ++r) {
+                    bool any = false;
+                    for (long lane = nsub - 1; lane > 0; --lane) {         // (downwards: lane - 1 still holds the last round's exit)
+                        const SubState ne = {ex_p[lane - 1], ex_s[lane - 1]}, e = {en_p[lane], en_s[lane]};
+                        any = any || hit[lane];
+                        if (!sub_differs(ne, e) && !(hit[lane] && lane <= r)) continue;
+                        any = true;
+                        SubState x = ne;
+                        cnt[lane] = (int)sub_walk<false>(x, cx, hi_of(lane), false, lane <= r, budget, img, m0, 0, nblk, bad);
+                        hit[lane] = bad && lane > r;
+                        en_p[lane] = ne.p; en_s[lane] = ne.s; ex_p[lane] = x.p; ex_s[lane] = x.s;
+                    }
+                    if (!any) break;
+                    ++rounds;
+                }
+                long first = base_blk;
+                for (long lane = 0; lane < nsub; ++lane) {
+                    SubState t = {en_p[lane], en_s[lane]};
+                    bool lane_bad = false;
+                    sub_walk<true>(t, cx, hi_of(lane), false, true, budget, img, m0, first, nblk, lane_bad);
+                    if (lane_bad) status[f] = EDITOR_JPEG_CORRUPT;
+                    first += cnt[lane];
+                }
+                car.p = ex_p[nsub - 1]; car.s = ex_s[nsub - 1]; base_blk = first;
+                ++chunks;
+            }
+            if (!((car.s >> 12) & SUB_ERR) && base_blk < nblk) {
+                SubCtx tc = cx;
+                tc.base = 0; tc.lim = 0;
+                SubState t = {car.p, car.s & ~7};
+                bool tail_bad = false;
+                sub_walk<true>(t, tc, 0, true, true, (nblk - base_blk) * 64 + 64, img, m0, base_blk, nblk, tail_bad);
+                if (tail_bad) status[f] = EDITOR_JPEG_CORRUPT;
+            }
+            const long per = (nblk + SPLIT_LANES - 1) / SPLIT_LANES;
+            uint32_t pred[3] = {0, 0, 0};
+            uint32_t sums[SPLIT_LANES][3];
+            for (long lane = 0; lane < SPLIT_LANES; ++lane) {
+                const long b0 = lane * per < nblk ? lane * per : nblk, b1 = b0 + per < nblk ? b0 + per : nblk;
+                sums[lane][0] = sums[lane][1] = sums[lane][2] = 0;
+                dc_lane_sum(g, img, m0, b0, b1, sums[lane]);
+            }
+            for (long lane = 0; lane < SPLIT_LANES; ++lane) {
+                const long b0 = lane * per < nblk ? lane * per : nblk, b1 = b0 + per < nblk ? b0 + per : nblk;
+                uint32_t mine[3] = {pred[0], pred[1], pred[2]};           // the exclusive prefix sum of the lanes' sums
+                dc_lane_apply(g, img, m0, b0, b1, mine);
+                for (int c = 0; c < 3; ++c) pred[c] += sums[lane][c];
+            }
+            stats[s * 2] = rounds; stats[s * 2 + 1] = chunks;
+        }
+        done = upto;
+    }
+    return 0;
+}
+
+extern "C" int editor_jpeg_entropy_split_device(const uint8_t* bytes, long nbytes, const int* fdesc_host, const long* ftab_host,
+                                                const long* seg_host, const int* fdesc, const long* ftab, const long* seg, const uint8_t* huff,
+                                                int nhuff, int B, long nseg, int sub_bytes, void* workspace, long workspace_bytes, int16_t* coef,
+                                                long coef_blocks, int* status, hipStream_t stream)
+{
+    if (!bytes || !fdesc_host || !ftab_host || !seg_host || !fdesc || !ftab || !seg || !huff || !workspace || !coef || !status)
+        return (int)hipErrorInvalidValue;
+    if (((uintptr_t)bytes & 15) || (nbytes & 15) || ((uintptr_t)coef & 15)) return (int)hipErrorInvalidValue;      // as editor_jpeg_entropy_device
+    long ws = 0;
+    if (editor_jpeg_entropy_split_workspace(nseg, sub_bytes, &ws) || workspace_bytes < ws || ((uintptr_t)workspace & 7)) return (int)hipErrorInvalidValue;
+    if (!check_entropy_tables(nbytes, fdesc_host, ftab_host, seg_host, nhuff, B, nseg, coef_blocks)) return (int)hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(status, 0, (size_t)B * sizeof(int), stream);
+    if (e != hipSuccess) return (int)e;
+    if (nseg == 0) return 0;
+    const size_t lds = (size_t)split_window_bytes(sub_bytes) + SPLIT_LDS_FIXED;
+    hipLaunchKernelGGL(jpeg_entropy_split_kernel, dim3((unsigned)nseg), dim3(SPLIT_LANES), lds, stream, bytes, nbytes, fdesc, ftab, seg, huff, B,
+                       nseg, sub_bytes, coef, status, (long*)workspace);
     EDITOR_LAUNCH_CHECK();
     return 0;
 }

@@ -424,14 +424,24 @@ class DeviceJpegDecoder:
     restart markers (if an interval is defined) all present and in order.  Every other file the parser accepts (progressive,
     several scans, irregular restarts) is decoded on the host as before and its coefficients copied in - a documented routing
     rule.  Same errors, same text; the one difference: corrupt ENTROPY data is found after the launch (the status
-    vector is read back before the call returns), not before it."""
+    vector is read back before the call returns), not before it.
 
-    def __init__(self, crop_w=256, threads=8, entropy="host"):
+    entropy="device_split" is the same path with editor_jpeg_entropy_split_device as its decoder: parallel INSIDE a segment too
+    (256 lanes per segment, each decoding split_sub_bytes of it, re-run from the left neighbour's exit state until the states
+    agree), so a batch's time no longer follows its longest restart-less file.  The setting for batches that hold long files
+    (tens of KB and more); eligibility, routing, errors and the coefficients are those of "device"."""
+
+    SPLIT_SUB_BYTES = 64                                     # (the sweep: profiles/device_entropy_split_time.txt)
+
+    def __init__(self, crop_w=256, threads=8, entropy="host", split_sub_bytes=None):
         from concurrent.futures import ThreadPoolExecutor
         from . import _lib
-        if entropy not in ("host", "device"):
-            raise ValueError("DeviceJpegDecoder: entropy is 'host' or 'device'")
+        if entropy not in ("host", "device", "device_split"):
+            raise ValueError("DeviceJpegDecoder: entropy is 'host', 'device' or 'device_split'")
         self.entropy = entropy
+        self.split_sub_bytes = int(self.SPLIT_SUB_BYTES if split_sub_bytes is None else split_sub_bytes)
+        if self.split_sub_bytes not in (16, 32, 64, 128):
+            raise ValueError("DeviceJpegDecoder: split_sub_bytes is 16, 32, 64 or 128")
         self.last_h2d_bytes = 0                              # bytes the last call copied to the device (tools/ragged_input_time.py)
         self.crop_w = int(crop_w)
         self._cd = _lib.lib().cdll
@@ -533,7 +543,7 @@ class DeviceJpegDecoder:
     def _device_entropy(self, files, bp, coef_d, block_off, device, extra=()):
         """Fills coef_d (flat int16 device tensor) at block_off[i] for every file of the planned batch: ONE host-to-device copy
         of the eligible files' scan bytes + descriptor tables (+ the caller's `extra` arrays) and one launch of
-        editor_jpeg_entropy_device; a host-routed file is decoded by editor_jpeg_entropy_decode on the pool and its range copied
+        editor_jpeg_entropy_device (entropy="device_split": editor_jpeg_entropy_split_device); a host-routed file is decoded by editor_jpeg_entropy_decode on the pool and its range copied
         (one copy per such file).  -> (status tensor, device views of extra)."""
         b = len(files)
         nbytes, spans, fdesc, ftab, segs, huff, nseg = self.pack_batch(files, bp, block_off)
@@ -576,9 +586,17 @@ class DeviceJpegDecoder:
             self.last_h2d_bytes = o
             dev = [blob_d[at:at + a.nbytes] for a, at in zip(parts, offs)]
             status = torch.empty(b, dtype=torch.int32, device=device)
-            call("editor_jpeg_entropy_device", blob_d[:nbytes], nbytes, ctypes.c_void_p(fdesc.ctypes.data), ctypes.c_void_p(ftab.ctypes.data),
-                 ctypes.c_void_p(segs.ctypes.data), dev[0].view(torch.int32), dev[1].view(torch.int64), dev[2].view(torch.int64), dev[3],
-                 int(huff.shape[0]), b, nseg, coef_d, coef_blocks, status)
+            tables = (blob_d[:nbytes], nbytes, ctypes.c_void_p(fdesc.ctypes.data), ctypes.c_void_p(ftab.ctypes.data),
+                      ctypes.c_void_p(segs.ctypes.data), dev[0].view(torch.int32), dev[1].view(torch.int64), dev[2].view(torch.int64), dev[3],
+                      int(huff.shape[0]), b, nseg)
+            if self.entropy == "device_split":
+                ws = ctypes.c_long(0)
+                if self._cd.editor_jpeg_entropy_split_workspace(nseg, self.split_sub_bytes, ctypes.byref(ws)):
+                    raise RuntimeError("editor_jpeg_entropy_split_workspace refused %d segments" % nseg)
+                work = torch.empty(ws.value // 8, dtype=torch.int64, device=device)
+                call("editor_jpeg_entropy_split_device", *tables, self.split_sub_bytes, work, ws.value, coef_d, coef_blocks, status)
+            else:
+                call("editor_jpeg_entropy_device", *tables, coef_d, coef_blocks, status)
         return status, dev[4:]
 
     @staticmethod
@@ -650,7 +668,7 @@ class DeviceJpegDecoder:
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("DeviceJpegDecoder reconstructs on the GPU (no CPU fallback)")
-        if self.entropy == "device":
+        if self.entropy != "host":
             return self._call_device(files, device)
         infos = [self.parse(f) for f in files]
         w, h = int(infos[0][0]), int(infos[0][1])
@@ -704,7 +722,7 @@ class DeviceJpegDecoder:
         b = len(files)
         if b < 1:
             raise ValueError("DeviceJpegDecoder.decode_ragged: empty batch")
-        if self.entropy == "device":
+        if self.entropy != "host":
             return self._decode_ragged_device(files, device)
         infos = np.zeros((b, 16), dtype=np.int32)
         for i, rc in enumerate(self._pool.map(lambda i: self._parse_rc(files[i], infos[i]), range(b))):
@@ -752,7 +770,7 @@ def load_modalities(files_by_modality, size, interpolation=3, device="cuda", ent
     """The separate-file sample layout (RGBNT201 / MSVR310: img_path is a list of one path per modality, each file resized on
     its own, data/datasets/bases.py:22-30).  files_by_modality: nmod lists of B byte strings -> nmod uint8 (B,Hout,Wout,3)
     tensors in the order given: ONE ragged decode + ONE ragged resize over all nmod * B files.  entropy: where the Huffman
-    decode runs, as DeviceJpegDecoder's keyword ("host", the default, or "device")."""
+    decode runs, as DeviceJpegDecoder's keyword ("host", the default, "device" or "device_split")."""
     if torch.device(device).type != "cuda":
         raise RuntimeError("load_modalities decodes on the GPU (no CPU fallback)")
     groups = [list(g) for g in files_by_modality]

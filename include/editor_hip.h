@@ -547,6 +547,28 @@ int editor_jpeg_entropy_device(const uint8_t* bytes, long nbytes, const int* fde
                                const long* seg_host, const int* fdesc, const long* ftab, const long* seg, const uint8_t* huff,
                                int nhuff, int B, long nseg, int16_t* coef, long coef_blocks, int* status,
                                editor_stream_t stream);
+/* The same decode, PARALLEL INSIDE A SEGMENT (DeviceJpegDecoder(entropy="device_split")): for files without restart markers,
+ * which are one segment each.  A segment's bytes are cut every sub_bytes (a power of two, 16 to 128); one lane decodes one
+ * subsequence, first from a guessed state, then again from its left neighbour's exit state until no exit state changes
+ * (self-synchronising Huffman decoding); 256 subsequences make a chunk, and one 256-thread workgroup walks its segment chunk
+ * by chunk, carrying the exact state.  Same tables, same checks, same coefficients and status as the entries above - bit for
+ * bit, whatever the data; only the time differs (it follows a file's length / 256, not its length).
+ * HOST: bytes of workspace either entry needs (the library never allocates); 8-byte aligned.  It returns as (nseg,2) int64:
+ * rounds run and chunks walked per segment - equal for both entries. */
+int editor_jpeg_entropy_split_workspace(long nseg, int sub_bytes, long* bytes);
+/* HOST twin: all pointers host memory; the kernel's routines, its lanes and rounds run one after another.
+ * hipErrorInvalidValue (nothing written) for tables editor_jpeg_entropy_segments refuses, a sub_bytes that is not accepted or
+ * a workspace that is too small. */
+int editor_jpeg_entropy_split_segments(const uint8_t* bytes, long nbytes, const int* fdesc, const long* ftab, const long* seg,
+                                       const uint8_t* huff, int nhuff, int B, long nseg, int sub_bytes, void* workspace,
+                                       long workspace_bytes, int16_t* coef, long coef_blocks, int* status);
+/* DEVICE: one 256-thread workgroup per segment of the batch; pointers as editor_jpeg_entropy_device, workspace in device
+ * memory.  status is written on the stream. */
+int editor_jpeg_entropy_split_device(const uint8_t* bytes, long nbytes, const int* fdesc_host, const long* ftab_host,
+                                     const long* seg_host, const int* fdesc, const long* ftab, const long* seg,
+                                     const uint8_t* huff, int nhuff, int B, long nseg, int sub_bytes, void* workspace,
+                                     long workspace_bytes, int16_t* coef, long coef_blocks, int* status,
+                                     editor_stream_t stream);
 
 /* T.Resize(size, interpolation) of decoded uint8 images (make_dataloader.py:246,256; torchvision 0.14.1 ->
  * PIL.Image.resize = Pillow ImagingResample, 8-bit path): horizontal pass then vertical pass with 22-bit fixed-point taps.

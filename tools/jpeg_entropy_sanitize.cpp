@@ -1,5 +1,7 @@
-// Stand-alone sanitizer harness for the HOST side of the device-side JPEG entropy decode: editor_jpeg_plan and
-// editor_jpeg_entropy_segments (the routine jpeg_entropy_kernel runs, compiled for the CPU).  For every file given: a cut every 7
+// Stand-alone sanitizer harness for the HOST side of the device-side JPEG entropy decode: editor_jpeg_plan,
+// editor_jpeg_entropy_segments (the routine jpeg_entropy_kernel runs, compiled for the CPU) and editor_jpeg_entropy_split_segments
+// (the routines jpeg_entropy_split_kernel runs, at sub_bytes 16 and 64, whose status and - for status 0 - coefficients must equal
+// the former's).  For every file given: a cut every 7
 // bytes (the sweep of tests/test_jpeg_host.py) and, for files under 6000 bytes, every single-bit flip of the whole file, each from
 // an exact-size heap copy so an overrun of one byte is seen.  Host code only; nothing here touches a GPU.
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
@@ -13,6 +15,9 @@
 extern "C" int editor_jpeg_plan(const uint8_t*, long, int*, int*, uint16_t*, uint8_t*, long*, long);
 extern "C" int editor_jpeg_entropy_segments(const uint8_t*, long, const int*, const long*, const long*, const uint8_t*, int, int, long, int16_t*,
                                             long, int*);
+extern "C" int editor_jpeg_entropy_split_workspace(long, int, long*);
+extern "C" int editor_jpeg_entropy_split_segments(const uint8_t*, long, const int*, const long*, const long*, const uint8_t*, int, int, long, int, void*,
+                                                  long, int16_t*, long, int*);
 
 static std::vector<uint8_t> read_file(const char* p)
 {
@@ -49,6 +54,23 @@ static int one(const uint8_t* d, long n, long* stats)
     rc = editor_jpeg_entropy_segments(bytes.data(), e1 - s0, fdesc, ftab, segs.data(), pool.data(), 6, 1, plan[1], coef.data(), info[8], &status);
     if (rc) { printf("tables refused: %d\n", rc); return 1; }
     stats[status ? 3 : 2]++;
+    for (int sub : {16, 64}) {
+        long need = 0;
+        if (editor_jpeg_entropy_split_workspace(plan[1], sub, &need)) { printf("workspace query refused\n"); return 1; }
+        std::vector<long> ws((size_t)need / 8);
+        // decoded twice into buffers that start out different: what comes back equal was written (a damaged stream can
+        // decode to any value, so no single fill pattern proves that)
+        std::vector<int16_t> coef2((size_t)info[8] * 64, (int16_t)0x5A5A), coef3((size_t)info[8] * 64, (int16_t)0x25A5);
+        int status2 = -1, status3 = -1;
+        rc = editor_jpeg_entropy_split_segments(bytes.data(), e1 - s0, fdesc, ftab, segs.data(), pool.data(), 6, 1, plan[1], sub, ws.data(), need,
+                                                coef2.data(), info[8], &status2);
+        if (rc) { printf("split: tables refused: %d\n", rc); return 1; }
+        rc = editor_jpeg_entropy_split_segments(bytes.data(), e1 - s0, fdesc, ftab, segs.data(), pool.data(), 6, 1, plan[1], sub, ws.data(), need,
+                                                coef3.data(), info[8], &status3);
+        if (rc || status2 != status || status3 != status) { printf("split %d: status %d, %d against %d (%ld bytes)\n", sub, status2, status3, status, n); return 1; }
+        if (!status && memcmp(coef.data(), coef2.data(), coef.size() * 2)) { printf("split %d: coefficients differ (%ld bytes)\n", sub, n); return 1; }
+        if (memcmp(coef2.data(), coef3.data(), coef2.size() * 2)) { printf("split %d: a block was left unwritten (%ld bytes)\n", sub, n); return 1; }
+    }
     return 0;
 }
 

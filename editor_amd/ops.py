@@ -539,10 +539,11 @@ def gemm(a, b, c, m, n, k, lda, ldb, ldc, trans_a=0, trans_b=0, alpha=1.0, beta=
             # kernel (LDS-DMA, deterministic split-K slabs) takes the whole tiles and a single-split product adds the
             # < 64-row tail - instead of the generic kernel with fp32-atomic split-K for the whole reduction
             k0 = (k // 64) * 64
-            gemm(a, b, c, m, n, k0, lda, ldb, ldc, 1, 1, alpha=alpha, splitk=splitk, a_off=a_off, b_off=b_off, c_off=c_off,
-                 epilogue=epilogue)
-            gemm(a, b, c, m, n, k - k0, lda, ldb, ldc, 1, 1, alpha=alpha, beta=1.0, splitk=1, a_off=a_off + k0 * lda,
-                 b_off=b_off + k0 * ldb, c_off=c_off)
+            # (the bias goes with the first product alone; the row scale is linear, so both take it)
+            gemm(a, b, c, m, n, k0, lda, ldb, ldc, 1, 1, alpha=alpha, bias=bias, rowscale=rowscale, splitk=splitk, a_off=a_off,
+                 b_off=b_off, c_off=c_off, epilogue=epilogue)
+            gemm(a, b, c, m, n, k - k0, lda, ldb, ldc, 1, 1, alpha=alpha, beta=1.0, rowscale=rowscale, splitk=1,
+                 a_off=a_off + k0 * lda, b_off=b_off + k0 * ldb, c_off=c_off)
             return
         th = ((int(epilogue) >> 12) & 15) * 16 or 256            # explicit EPI_TILE_ROWS, else the shape heuristic
         if (SHORT_TILES and not trans_a and not trans_b and splitk == 1 and beta == 0.0 and (m_live is None or live_dense) and m >= 2048

@@ -51,7 +51,8 @@ typedef struct ihipStream_t* editor_stream_t;   /* == hipStream_t */
                                   * lockstep and one CU's HBM-bound epilogue runs beside the others' K loops.  Same results bit
                                   * for bit.  The caller picks c ~ one tile period (editor_amd.ops.gemm_stagger). */
 #define EDITOR_EPI_TILE_ROWS(h) ((((h) / 16) & 15) << 12) /* OR-able, h = 208 | 256 (ping-pong kernel, both operands k-major,
-                                   * split-K 1, beta 0): rows per output tile.  M = 49 536 token rows x 768 columns are 582 full
+                                   * split-K 1, beta 0, M >= 256, N >= 256 and N, ldc, ldaux multiples of 8, K % 64 == 0): rows per
+                                   * output tile.  M = 49 536 token rows x 768 columns are 582 full
                                    * tiles = 2.27 rounds of the 256 CUs; 208-row tiles make it 2.8 rounds of smaller tiles.
                                    * EDITOR_EPI_COLSUM then writes ceil(M / h) partial rows.  hipErrorInvalidValue when the
                                    * conditions do not hold; the caller picks h (editor_amd.ops.gemm_tile_rows). */

@@ -50,10 +50,14 @@ def make_cfg(size_train=(256, 128), al=1, transformer_type="vit_base_patch16_224
     solver = SimpleNamespace(OPTIMIZER_NAME="SGD", MAX_EPOCHS=70, BASE_LR=0.001, LARGE_FC_LR=False, BIAS_LR_FACTOR=2,
                              MOMENTUM=0.9, WEIGHT_DECAY=0.0001, WEIGHT_DECAY_BIAS=0.0001, WARMUP_ITERS=10,
                              CENTER_LR=0.5, MARGIN=0.3, SEED=1111, IMS_PER_BATCH=128)
+    # config/defaults.py:66-93,161 (the keys data/datasets/make_dataloader.py reads; editor_amd.data.make_dataloader)
     return SimpleNamespace(MODEL=model, SOLVER=solver,
                            DATALOADER=SimpleNamespace(SAMPLER="softmax_triplet", NUM_INSTANCE=16, NUM_WORKERS=14),
                            INPUT=SimpleNamespace(SIZE_TRAIN=list(size_train),
-                                                 SIZE_TEST=list(size_train)))
+                                                 SIZE_TEST=list(size_train), PROB=0.5, RE_PROB=0.5, PADDING=10,
+                                                 PIXEL_MEAN=[0.5, 0.5, 0.5], PIXEL_STD=[0.5, 0.5, 0.5]),
+                           DATASETS=SimpleNamespace(NAMES="RGBNT201", ROOT_DIR="./data"),
+                           TEST=SimpleNamespace(IMS_PER_BATCH=64))
 
 
 def preset(name, **over):

@@ -8,6 +8,8 @@ Host side (Python, as in the reference) + one HIP kernel (csrc/augment.hip):
                                from Python's `random`, returned as numbers instead of applied (golden-pinned)
     DeviceTrainTransform       T.RandomHorizontalFlip -> T.Pad -> T.RandomCrop -> T.ToTensor -> T.Normalize ->
                                RandomErasing(mode='pixel') of make_dataloader.py:245-253 for a whole batch in one launch
+    make_dataloader            data/datasets/make_dataloader.py:244-308: the reference's 7-tuple, its three loaders being
+                               DeviceBatchLoader (editor_amd/loader.py) over list_dataset (editor_amd/datasets.py)
     DeviceJpegDecoder / DeviceResize   `Image.open(path).convert('RGB')` + T.Resize: the stitched layout (one 768x128 file, three
                                256-wide crops: RGBNT100 / RGBNT300) through __call__, the separate-file layout (one detector
                                crop of any size per modality: RGBNT201 / MSVR310) through decode_ragged + RaggedImages +
@@ -158,18 +160,20 @@ class ErasingParams:
         max_aspect = max_aspect or 1 / min_aspect
         self.log_aspect_ratio = (math.log(min_aspect), math.log(max_aspect))
 
-    def __call__(self, img_h, img_w):
-        if random.random() > self.probability:
+    def __call__(self, img_h, img_w, rng=None):
+        """rng: a random.Random to draw from instead of the global `random` (editor_amd/loader.py: the worker thread's own)."""
+        rng = random if rng is None else rng
+        if rng.random() > self.probability:
             return (0, 0, 0, 0, 0)
         area = img_h * img_w
         for _ in range(10):
-            target_area = random.uniform(self.min_area, self.max_area) * area
-            aspect_ratio = math.exp(random.uniform(*self.log_aspect_ratio))
+            target_area = rng.uniform(self.min_area, self.max_area) * area
+            aspect_ratio = math.exp(rng.uniform(*self.log_aspect_ratio))
             h = int(round(math.sqrt(target_area * aspect_ratio)))
             w = int(round(math.sqrt(target_area / aspect_ratio)))
             if w < img_w and h < img_h:
-                top = random.randint(0, img_h - h)
-                left = random.randint(0, img_w - w)
+                top = rng.randint(0, img_h - h)
+                left = rng.randint(0, img_w - w)
                 return (1, top, left, h, w)
         return (0, 0, 0, 0, 0)
 
@@ -362,15 +366,16 @@ class DeviceTrainTransform:
         self.std = (ctypes.c_float * 3)(*std)
         self.erasing = ErasingParams(re_prob)
 
-    def draw(self, batch):
-        """Per-image parameter rows in the order the reference's per-image chain consumes its generators."""
+    def draw(self, batch, generator=None, rng=None):
+        """Per-image parameter rows in the order the reference's per-image chain consumes its generators: torch's global CPU
+        generator and Python's global `random`, or the caller's own torch.Generator / random.Random (the globals untouched)."""
         rows = []
         for _ in range(batch):
-            flip = int(torch.rand(1).item() < self.prob)
-            top = int(torch.randint(0, 2 * self.padding + 1, size=(1,)).item())
-            left = int(torch.randint(0, 2 * self.padding + 1, size=(1,)).item())
-            rows.append((flip, top, left) + self.erasing(self.h, self.w))
-        return torch.tensor(rows, dtype=torch.int32)
+            flip = int(torch.rand(1, generator=generator).item() < self.prob)
+            top = int(torch.randint(0, 2 * self.padding + 1, size=(1,), generator=generator).item())
+            left = int(torch.randint(0, 2 * self.padding + 1, size=(1,), generator=generator).item())
+            rows.append((flip, top, left) + self.erasing(self.h, self.w, rng=rng))
+        return torch.tensor(rows, dtype=torch.int32).reshape(batch, 8)
 
     def __call__(self, images_u8, params=None, noise=None, seed=0):
         """images_u8: uint8 (B,H,W,3) on the device.  params: int32 (B,8) from draw() (drawn here if None).
@@ -789,3 +794,33 @@ def load_modalities(files_by_modality, size, interpolation=3, device="cuda", ent
         rs = _DEFAULT[key] = DeviceResize(size, interpolation)
     out = rs(dec.decode_ragged([f for g in groups for f in g], device))
     return [out[m * b:(m + 1) * b] for m in range(len(groups))]
+
+
+def make_dataloader(cfg, rank=None, world_size=None):
+    """data/datasets/make_dataloader.py:244-308 -> (train_loader, train_loader_normal, val_loader, num_query, num_classes,
+    cam_num, view_num); the loaders are DeviceBatchLoader: the reference's batch tuples with the images already on the device.
+    rank / world_size (MODEL.DIST_TRAIN only) default to torch.distributed's."""
+    from .datasets import list_dataset
+    from .loader import DeviceBatchLoader
+    ds = list_dataset(cfg.DATASETS.NAMES, cfg.DATASETS.ROOT_DIR)
+    inp = cfg.INPUT
+    common = dict(seed=int(cfg.SOLVER.SEED), mean=tuple(inp.PIXEL_MEAN), std=tuple(inp.PIXEL_STD))
+    aug = dict(prob=inp.PROB, padding=inp.PADDING, re_prob=inp.RE_PROB, **common)
+    ims, kind = int(cfg.SOLVER.IMS_PER_BATCH), cfg.DATALOADER.SAMPLER
+    if "triplet" in kind:
+        if cfg.MODEL.DIST_TRAIN:
+            sampler = RandomIdentitySampler_DDP(ds.train, ims, cfg.DATALOADER.NUM_INSTANCE, rank=rank, world_size=world_size)
+            batches = torch.utils.data.sampler.BatchSampler(sampler, ims // sampler.world_size, True)
+            train_loader = DeviceBatchLoader(ds.train, ims // sampler.world_size, inp.SIZE_TRAIN, True, batch_sampler=batches, **aug)
+        else:
+            sampler = RandomIdentitySampler(ds.train, ims, cfg.DATALOADER.NUM_INSTANCE)
+            train_loader = DeviceBatchLoader(ds.train, ims, inp.SIZE_TRAIN, True, sampler=sampler, **aug)
+    elif kind == "softmax":
+        train_loader = DeviceBatchLoader(ds.train, ims, inp.SIZE_TRAIN, True, sampler=torch.utils.data.RandomSampler(ds.train), **aug)   # (shuffle=True)
+    else:
+        raise ValueError("unsupported sampler! expected softmax or triplet but got {}".format(kind))
+    test_ims = int(cfg.TEST.IMS_PER_BATCH)
+    val_loader = DeviceBatchLoader(ds.query + ds.gallery, test_ims, inp.SIZE_TEST, False, **common)
+    train_loader_normal = DeviceBatchLoader(ds.train, test_ims, inp.SIZE_TEST, False, **common)
+    return train_loader, train_loader_normal, val_loader, len(ds.query), ds.num_train_pids, ds.num_train_cams, ds.num_train_vids
+

@@ -727,8 +727,14 @@ __host__ __device__ inline void lut_fill(HuffLut& t, const uint8_t* dht, int lan
 }
 
 // BitReader over a WINDOW of the stream: buf[0] is stream byte `base`, bytes [base, lim) are present.  The host hands the
-// whole stream (base 0, lim = its length); the kernel restages the window between blocks (SEG_MARGIN).
-struct SegReader {
+// whole stream (base 0, lim = its length); the kernels restage the window (SEG_MARGIN, SPLIT_MARGIN).
+// TRACK: the reader can also say where it is - which loaded bytes took two stream bytes (`stuffed`, newest in bit 0) and how
+// many of the loaded bits are the zeros fed past the data (`vbits`, always the newest).  Without it those two members and
+// every statement that keeps them do not exist.
+template <bool TRACK> struct ReaderTrack {};
+template <> struct ReaderTrack<true> { int vbits; uint32_t stuffed; };
+template <bool TRACK>
+struct WinReader : ReaderTrack<TRACK> {
     const uint8_t* buf; long base, lim;
     long p, end;                                   // next byte; end of the segment
     uint64_t acc; int nbits; bool marker;
@@ -743,6 +749,7 @@ struct SegReader {
                 if (b0 != 0xFF && b1 != 0xFF && b2 != 0xFF && b3 != 0xFF) {
                     acc = (acc << 32) | ((b0 << 24) | (b1 << 16) | (b2 << 8) | b3);
                     nbits += 32; p += 4;
+                    if constexpr (TRACK) this->stuffed <<= 4;
                     continue;
                 }
             }
@@ -750,12 +757,13 @@ struct SegReader {
             if (!marker && p < end && p >= base && p < lim) {
                 b = buf[p - base];
                 if (b == 0xFF) {
-                    if (p + 1 < end && p + 1 < lim && buf[p + 1 - base] == 0x00) p += 2;
+                    if (p + 1 < end && p + 1 < lim && buf[p + 1 - base] == 0x00) { p += 2; if constexpr (TRACK) this->stuffed = (this->stuffed << 1) | 1u; }
                     else { marker = true; b = 0; }
-                } else ++p;
+                } else { ++p; if constexpr (TRACK) this->stuffed <<= 1; }
             } else {
                 marker = true;
             }
+            if constexpr (TRACK) { if (marker && this->vbits < 64) this->vbits += 8; }   // (64 or more: everything held is past the data)
             acc = (acc << 8) | b;
             nbits += 8;
         }
@@ -763,9 +771,28 @@ struct SegReader {
     __host__ __device__ __forceinline__ int peek(int n) { if (nbits < n) fill(); return (int)((acc >> (nbits - n)) & ((1u << n) - 1)); }
     __host__ __device__ __forceinline__ void drop(int n) { nbits -= n; }
     __host__ __device__ __forceinline__ int get(int n) { if (n == 0) return 0; const int v = peek(n); drop(n); return v; }
+    // ---- TRACK only ----
+    __host__ __device__ __forceinline__ void seek(long at, int bit) {
+        p = at; acc = 0; nbits = 0; this->vbits = 0; this->stuffed = 0; marker = false;
+        if (bit) { peek(bit); drop(bit); }
+    }
+    // all data consumed and the reader has met its end (call after fill())
+    __host__ __device__ __forceinline__ bool exhausted() const { return marker && nbits <= this->vbits; }
+    // the stream position of the next unconsumed bit: the bytes still held are walked back over, a stuffed one counting two
+    __host__ __device__ __forceinline__ void cursor(long& cp, int& cbit) const {
+        const int real = nbits - this->vbits;
+        if (real <= 0) { cp = p; cbit = 0; return; }
+        const int part = real & 7, cnt = (real + 7) >> 3;                     // (cnt <= 7: at most 56 bits are held)
+        cp = p - cnt - __builtin_popcount(this->stuffed & ((1u << cnt) - 1u));
+        cbit = part ? 8 - part : 0;
+    }
 };
+using SegReader = WinReader<false>;
+using SubReader = WinReader<true>;
 
-__host__ __device__ __forceinline__ int seg_huff(SegReader& br, const HuffLut& t)
+// one Huffman symbol from either reader: the 9-bit lookahead, then the per-length rows; -1 = no such code
+template <class R>
+__host__ __device__ __forceinline__ int huff_symbol(R& br, const HuffLut& t)
 {
     const int e = t.look[br.peek(9)];
     if (e) { br.drop(e >> 8); return e & 0xff; }
@@ -835,7 +862,7 @@ __host__ __device__ __forceinline__ int decode_segment_blocks(SegState& st, cons
         const long dst = scan_block(g, m0, st.blk, c);
         if (dst < 0 || dst >= g.total_blocks) return EDITOR_JPEG_CORRUPT;     // (cannot happen: see scan_block)
         int16_t* blk = img + dst * 64;
-        const int sdc = seg_huff(br, lut[c]);
+        const int sdc = huff_symbol(br, lut[c]);
         if (sdc < 0 || sdc > 11) return EDITOR_JPEG_CORRUPT;
         const int diff = sdc ? seg_extend(br.get(sdc), sdc) : 0;
         int pred = (c == 0 ? st.pred0 : (c == 1 ? st.pred1 : st.pred2)) + diff;
@@ -843,7 +870,7 @@ __host__ __device__ __forceinline__ int decode_segment_blocks(SegState& st, cons
         blk[0] = (int16_t)pred;
         const HuffLut& ac = lut[3 + c];
         for (int kk = 1; kk < 64;) {
-            const int rs = seg_huff(br, ac);
+            const int rs = huff_symbol(br, ac);
             if (rs < 0) return EDITOR_JPEG_CORRUPT;
             const int r = rs >> 4, sz = rs & 15;
             if (sz == 0) { if (r == 15) { kk += 16; continue; } break; }
@@ -899,6 +926,62 @@ bool check_entropy_tables(long nbytes, const int* fdesc, const long* ftab, const
     return done == nseg;
 }
 
+// One restart segment of the batch as either decoder sees it: whose it is, which blocks it holds, where its bytes are.
+struct SegDesc {
+    int f;                                         // the file
+    ScanGeom g;
+    long m0, nblk;                                 // first MCU; blocks
+    long start, end;                               // its bytes, in `bytes`
+    int16_t* img;                                  // the file's first coefficient block
+};
+// segment s, which belongs to file f (tables validated by check_entropy_tables before anything runs)
+__host__ __device__ __forceinline__ bool seg_describe(SegDesc& d, int f, const int* fdesc, const long* ftab, const long* seg, int16_t* coef, int B, long s)
+{
+    d.f = f;
+    if (!make_scan_geom(fdesc + (long)f * 16, d.g)) return false;
+    d.m0 = seg[s * 3 + 2];
+    const long m1 = d.g.restart && d.m0 + d.g.restart < d.g.nmcu ? d.m0 + d.g.restart : d.g.nmcu;
+    d.nblk = (m1 - d.m0) * d.g.bpm;
+    const long bo = ftab[(long)FT_BYTE * B + f];
+    d.start = bo + seg[s * 3]; d.end = bo + seg[s * 3 + 1];
+    d.img = coef + ftab[(long)FT_COEF * B + f] * 64;
+    return true;
+}
+
+// The kernels' prologue and window staging, `nlanes` lanes of one workgroup.  EVERY lane calls each of these, and none of
+// them holds a barrier: the barriers between them stand in the kernels' bodies.
+// the zigzag copy and the per-length rows of the scan's six tables (fd: the file's fdesc row) ...
+__device__ __forceinline__ void seg_tables_begin(HuffLut* lut, uint8_t* zigzag, const ScanGeom& g, const int* fd, const uint8_t* huff, int lane, int nlanes)
+{
+    if (nlanes == 64 || lane < 64) zigzag[lane] = kZigzagDev[lane];
+    if (lane < 6 && lane % 3 < g.ncomp) lut_lengths(lut[lane], huff + (long)fd[6 + lane] * DHT_BYTES);
+}
+// ... and, after a barrier, their values and lookahead entries
+__device__ __forceinline__ void seg_tables_fill(HuffLut* lut, const ScanGeom& g, const int* fd, const uint8_t* huff, int lane, int nlanes)
+{
+    for (int t = 0; t < 6; ++t)
+        if (t % 3 < g.ncomp) lut_fill(lut[t], huff + (long)fd[6 + t] * DHT_BYTES, lane, nlanes);
+}
+// zero the segment's blocks, 16 bytes per lane
+__device__ __forceinline__ void seg_zero_blocks(const SegDesc& d, int lane, int nlanes)
+{
+    for (long i = lane; i < d.nblk * 8; i += nlanes) {
+        int c;
+        const long dst = scan_block(d.g, d.m0, i >> 3, c);
+        *reinterpret_cast<uint4*>(d.img + dst * 64 + (i & 7) * 8) = make_uint4(0, 0, 0, 0);
+    }
+}
+// win[0, need) = bytes[wpos, wpos + need), 16 bytes per lane (wpos, win 16-byte aligned), zeros outside [0, nbytes)
+__device__ __forceinline__ void seg_stage_window(uint8_t* win, const uint8_t* __restrict__ bytes, long nbytes, long wpos, int need, int lane, int nlanes)
+{
+    for (int i = lane * 16; i < need; i += nlanes * 16) {
+        const long a = wpos + i;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (a >= 0 && a + 16 <= nbytes) v = *reinterpret_cast<const uint4*>(bytes + a);
+        *reinterpret_cast<uint4*>(win + i) = v;
+    }
+}
+
 // one 64-thread workgroup (one wave) per restart segment of the whole batch
 __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restrict__ bytes, long nbytes, const int* __restrict__ fdesc,
                                                           const long* __restrict__ ftab, const long* __restrict__ seg,
@@ -915,48 +998,28 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
     const int lane = threadIdx.x;
     const int f = ragged_find(ftab + (long)FT_SEGS * B, B, s);
     const int* fd = fdesc + (long)f * 16;
-    ScanGeom g;
-    if (!make_scan_geom(fd, g)) return;                                   // (validated on the host before the launch)
-    const long m0 = seg[s * 3 + 2];
-    const long m1 = g.restart && m0 + g.restart < g.nmcu ? m0 + g.restart : g.nmcu;
-    const long nblk = (m1 - m0) * g.bpm;
-    const long bo = ftab[(long)FT_BYTE * B + f];
-    const long start = bo + seg[s * 3], end = bo + seg[s * 3 + 1];        // in `bytes`
-    int16_t* img = coef + ftab[(long)FT_COEF * B + f] * 64;
+    SegDesc d;
+    if (!seg_describe(d, f, fdesc, ftab, seg, coef, B, s)) return;        // (validated on the host before the launch)
 
-    // the lookahead tables of this file's scan, all lanes
-    zigzag[lane] = kZigzagDev[lane];
-    const bool mine = lane < 6 && lane % 3 < g.ncomp;
-    if (mine) lut_lengths(lut[lane], huff + (long)fd[6 + lane] * DHT_BYTES);
+    seg_tables_begin(lut, zigzag, d.g, fd, huff, lane, EDITOR_WAVE);
     __syncthreads();
-    for (int t = 0; t < 6; ++t)
-        if (t % 3 < g.ncomp) lut_fill(lut[t], huff + (long)fd[6 + t] * DHT_BYTES, lane, EDITOR_WAVE);
-    // zero the segment's blocks, 16 bytes per lane
-    for (long i = lane; i < nblk * 8; i += EDITOR_WAVE) {
-        int c;
-        const long dst = scan_block(g, m0, i >> 3, c);
-        *reinterpret_cast<uint4*>(img + dst * 64 + (i & 7) * 8) = make_uint4(0, 0, 0, 0);
-    }
+    seg_tables_fill(lut, d.g, fd, huff, lane, EDITOR_WAVE);
+    seg_zero_blocks(d, lane, EDITOR_WAVE);
     __threadfence_block();
     __syncthreads();
 
     SegState st;
-    seg_begin(st, start, end);
-    long wpos = start & ~15L;
+    seg_begin(st, d.start, d.end);
+    long wpos = d.start & ~15L;
     int rc = SEG_REFILL;
-    for (long round = 0; round <= nblk && rc == SEG_REFILL; ++round) {   // (every round decodes at least one block)
-        const long need = end - wpos < SEG_WINDOW ? end - wpos : SEG_WINDOW;   // (the reader stops at the segment's end)
-        for (int i = lane * 16; i < need; i += EDITOR_WAVE * 16) {
-            const long a = wpos + i;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (a >= 0 && a + 16 <= nbytes) v = *reinterpret_cast<const uint4*>(bytes + a);
-            *reinterpret_cast<uint4*>(win + i) = v;
-        }
+    for (long round = 0; round <= d.nblk && rc == SEG_REFILL; ++round) { // (every round decodes at least one block)
+        const long need = d.end - wpos < SEG_WINDOW ? d.end - wpos : SEG_WINDOW;   // (the reader stops at the segment's end)
+        seg_stage_window(win, bytes, nbytes, wpos, (int)need, lane, EDITOR_WAVE);
         __syncthreads();
         if (lane == 0) {                                                  // one lane walks the bits
             st.br.buf = win; st.br.base = wpos;
             st.br.lim = wpos + SEG_WINDOW < nbytes ? wpos + SEG_WINDOW : nbytes;
-            verdict = decode_segment_blocks(st, g, lut, zigzag, img, m0, nblk);
+            verdict = decode_segment_blocks(st, d.g, lut, zigzag, d.img, d.m0, d.nblk);
             next_pos = st.br.p;
         }
         __syncthreads();
@@ -964,7 +1027,7 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
         wpos = next_pos & ~15L;
         __syncthreads();
     }
-    if (lane == 0 && rc != SEG_DONE) status[f] = EDITOR_JPEG_CORRUPT;
+    if (lane == 0 && rc != SEG_DONE) status[d.f] = EDITOR_JPEG_CORRUPT;
 }
 
 
@@ -1000,71 +1063,6 @@ inline bool split_sub_ok(int sub) { return sub >= SPLIT_SUB_MIN && sub <= SPLIT_
 //          SUB_ERR  absorbing: one of decode()'s three errors happened before this point (p and the rest are 0)
 struct SubState { long p; int s; };
 __host__ __device__ __forceinline__ bool sub_differs(const SubState& a, const SubState& b) { return a.p != b.p || a.s != b.s; }
-
-// SegReader that can say where it is: which loaded bytes took two stream bytes (`stuffed`, newest in bit 0) and how many of
-// the loaded bits are the zeros fed past the data (`vbits`, always the newest).
-struct SubReader {
-    const uint8_t* buf; long base, lim;            // the window, as SegReader's
-    long p, end;
-    uint64_t acc; int nbits, vbits; uint32_t stuffed; bool marker;
-    __host__ __device__ __forceinline__ void fill() {
-        while (nbits <= 24) {
-            if (!marker && p >= base && p + 4 <= end && p + 4 <= lim) {
-                const uint8_t* q = buf + (p - base);
-                const uint32_t b0 = q[0], b1 = q[1], b2 = q[2], b3 = q[3];
-                if (b0 != 0xFF && b1 != 0xFF && b2 != 0xFF && b3 != 0xFF) {
-                    acc = (acc << 32) | ((b0 << 24) | (b1 << 16) | (b2 << 8) | b3);
-                    nbits += 32; p += 4; stuffed <<= 4;
-                    continue;
-                }
-            }
-            uint8_t b = 0;
-            if (!marker && p < end && p >= base && p < lim) {
-                b = buf[p - base];
-                if (b == 0xFF) {
-                    if (p + 1 < end && p + 1 < lim && buf[p + 1 - base] == 0x00) { p += 2; stuffed = (stuffed << 1) | 1u; }
-                    else { marker = true; b = 0; }
-                } else { ++p; stuffed <<= 1; }
-            } else {
-                marker = true;
-            }
-            if (marker && vbits < 64) vbits += 8;                          // (64 or more: everything held is past the data)
-            acc = (acc << 8) | b;
-            nbits += 8;
-        }
-    }
-    __host__ __device__ __forceinline__ int peek(int n) { if (nbits < n) fill(); return (int)((acc >> (nbits - n)) & ((1u << n) - 1)); }
-    __host__ __device__ __forceinline__ void drop(int n) { nbits -= n; }
-    __host__ __device__ __forceinline__ int get(int n) { if (n == 0) return 0; const int v = peek(n); drop(n); return v; }
-    __host__ __device__ __forceinline__ void seek(long at, int bit) {
-        p = at; acc = 0; nbits = 0; vbits = 0; stuffed = 0; marker = false;
-        if (bit) { peek(bit); drop(bit); }
-    }
-    // all data consumed and the reader has met its end (call after fill())
-    __host__ __device__ __forceinline__ bool exhausted() const { return marker && nbits <= vbits; }
-    // the stream position of the next unconsumed bit: the bytes still held are walked back over, a stuffed one counting two
-    __host__ __device__ __forceinline__ void cursor(long& cp, int& cbit) const {
-        const int real = nbits - vbits;
-        if (real <= 0) { cp = p; cbit = 0; return; }
-        const int part = real & 7, cnt = (real + 7) >> 3;                     // (cnt <= 7: at most 56 bits are held)
-        cp = p - cnt - __builtin_popcount(stuffed & ((1u << cnt) - 1u));
-        cbit = part ? 8 - part : 0;
-    }
-};
-
-template <class R>
-__host__ __device__ __forceinline__ int sub_huff(R& br, const HuffLut& t)    // seg_huff, for either reader
-{
-    const int e = t.look[br.peek(9)];
-    if (e) { br.drop(e >> 8); return e & 0xff; }
-    const int code = br.peek(16);
-    for (int l = 10; l <= 16; ++l) {
-        const int c = code >> (16 - l);
-        if (c <= t.maxcode[l]) { br.drop(l); return t.vals[(c + t.valoff[l]) & 0xff]; }
-    }
-    br.drop(16);
-    return -1;
-}
 
 // what a walk reads: the scan's geometry and tables, and the staged window of the stream (as SegReader's buf / base / lim)
 struct SubCtx {
@@ -1121,13 +1119,13 @@ __host__ __device__ __forceinline__ long sub_walk(SubState& s, const SubCtx& cx,
             fresh = false;
         }
         if (k == 0) {
-            const int sdc = sub_huff(br, cx.lut[c]);
+            const int sdc = huff_symbol(br, cx.lut[c]);
             if (sdc < 0 || sdc > 11) { bad = true; if (exact) { s.p = 0; s.s = SUB_ERR << 12; return done; } k = 0; w = 0; continue; }
             const int diff = sdc ? seg_extend(br.get(sdc), sdc) : 0;
             if (WRITE) out[0] = (int16_t)diff;
             k = 1;
         } else {
-            const int rs = sub_huff(br, cx.lut[3 + c]);
+            const int rs = huff_symbol(br, cx.lut[3 + c]);
             if (rs < 0) { bad = true; if (exact) { s.p = 0; s.s = SUB_ERR << 12; return done; } k = 0; w = 0; continue; }
             const int r = rs >> 4, sz = rs & 15;
             if (sz == 0) {
@@ -1211,26 +1209,16 @@ __global__ __launch_bounds__(SPLIT_LANES) void jpeg_entropy_split_kernel(const u
     const int lane = threadIdx.x;
     const int f = ragged_find(ftab + (long)FT_SEGS * B, B, s);
     const int* fd = fdesc + (long)f * 16;
-    ScanGeom g;
-    if (!make_scan_geom(fd, g)) return;                                   // (validated on the host before the launch)
-    const long m0 = seg[s * 3 + 2];
-    const long m1 = g.restart && m0 + g.restart < g.nmcu ? m0 + g.restart : g.nmcu;
-    const long nblk = (m1 - m0) * g.bpm;
-    const long bo = ftab[(long)FT_BYTE * B + f];
-    const long start = bo + seg[s * 3], end = bo + seg[s * 3 + 1];        // in `bytes`
-    int16_t* img = coef + ftab[(long)FT_COEF * B + f] * 64;
+    SegDesc d;
+    if (!seg_describe(d, f, fdesc, ftab, seg, coef, B, s)) return;        // (validated on the host before the launch)
+    const ScanGeom& g = d.g;
+    const long m0 = d.m0, nblk = d.nblk, start = d.start, end = d.end;
+    int16_t* img = d.img;
 
-    if (lane < 64) zigzag[lane] = kZigzagDev[lane];
-    const bool mine = lane < 6 && lane % 3 < g.ncomp;
-    if (mine) lut_lengths(lut[lane], huff + (long)fd[6 + lane] * DHT_BYTES);
+    seg_tables_begin(lut, zigzag, g, fd, huff, lane, SPLIT_LANES);
     __syncthreads();
-    for (int t = 0; t < 6; ++t)
-        if (t % 3 < g.ncomp) lut_fill(lut[t], huff + (long)fd[6 + t] * DHT_BYTES, lane, SPLIT_LANES);
-    for (long i = lane; i < nblk * 8; i += SPLIT_LANES) {                 // zero the segment's blocks, 16 bytes per lane
-        int c;
-        const long dst = scan_block(g, m0, i >> 3, c);
-        *reinterpret_cast<uint4*>(img + dst * 64 + (i & 7) * 8) = make_uint4(0, 0, 0, 0);
-    }
+    seg_tables_fill(lut, g, fd, huff, lane, SPLIT_LANES);
+    seg_zero_blocks(d, lane, SPLIT_LANES);
     __threadfence_block();
     __syncthreads();
 
@@ -1247,12 +1235,7 @@ __global__ __launch_bounds__(SPLIT_LANES) void jpeg_entropy_split_kernel(const u
         const long c1 = c0 + chunk_bytes < end ? c0 + chunk_bytes : end;
         const long wpos = c0 & ~15L;
         const long need = c1 - wpos + SPLIT_MARGIN - 16 < wbytes ? c1 - wpos + SPLIT_MARGIN - 16 : wbytes;
-        for (long i = (long)lane * 16; i < need; i += SPLIT_LANES * 16) {
-            const long a = wpos + i;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (a >= 0 && a + 16 <= nbytes) v = *reinterpret_cast<const uint4*>(bytes + a);
-            *reinterpret_cast<uint4*>(win + i) = v;
-        }
+        seg_stage_window(win, bytes, nbytes, wpos, (int)need, lane, SPLIT_LANES);
         __syncthreads();
         cx.base = wpos;
         cx.lim = wpos + ((need + 15) & ~15L) < nbytes ? wpos + ((need + 15) & ~15L) : nbytes;
@@ -1319,6 +1302,56 @@ __global__ __launch_bounds__(SPLIT_LANES) void jpeg_entropy_split_kernel(const u
     if (lane == 0) { stats[s * 2] = rounds; stats[s * 2 + 1] = chunks; }
 }
 
+// The host twins' walk over a planned batch (tables checked by the caller): every file's status cleared; for a file with
+// segments its six tables built and its blocks zeroed, then body(s, segment, tables) for each of its segments in order.
+template <class Body>
+void for_each_segment(const int* fdesc, const long* ftab, const long* seg, const uint8_t* huff, int B, int16_t* coef, int* status, Body body)
+{
+    HuffLut lut[6];
+    long done = 0;
+    for (int f = 0; f < B; ++f) {
+        status[f] = 0;
+        const long upto = ftab[(long)FT_SEGS * B + f];
+        const int* fd = fdesc + (long)f * 16;
+        for (long s = done; s < upto; ++s) {
+            SegDesc d;
+            seg_describe(d, f, fdesc, ftab, seg, coef, B, s);
+            if (s == done) {
+                for (int t = 0; t < 6; ++t)
+                    if (t % 3 < d.g.ncomp) {
+                        const uint8_t* dht = huff + (long)fd[6 + t] * DHT_BYTES;
+                        lut_lengths(lut[t], dht);
+                        lut_fill(lut[t], dht, 0, 1);
+                    }
+                memset(d.img, 0, (size_t)d.g.total_blocks * 128);
+            }
+            body(s, d, lut);
+        }
+        done = upto;
+    }
+}
+
+// What the two device entries check before they launch, and the cleared status vector; 0 or the error to return.
+int entropy_device_begin(const uint8_t* bytes, long nbytes, const int* fdesc_host, const long* ftab_host, const long* seg_host, const int* fdesc,
+                         const long* ftab, const long* seg, const uint8_t* huff, int nhuff, int B, long nseg, int16_t* coef, long coef_blocks,
+                         int* status, hipStream_t stream)
+{
+    if (!bytes || !fdesc_host || !ftab_host || !seg_host || !fdesc || !ftab || !seg || !huff || !coef || !status)
+        return (int)hipErrorInvalidValue;
+    // the kernels stage 16 bytes per lane: the byte buffer is 16-byte aligned and a whole number of such pieces
+    if (((uintptr_t)bytes & 15) || (nbytes & 15) || ((uintptr_t)coef & 15)) return (int)hipErrorInvalidValue;
+    if (!check_entropy_tables(nbytes, fdesc_host, ftab_host, seg_host, nhuff, B, nseg, coef_blocks)) return (int)hipErrorInvalidValue;
+    if (nseg > 0x7fffffffL) return (int)hipErrorInvalidValue;
+    return (int)hipMemsetAsync(status, 0, (size_t)B * sizeof(int), stream);
+}
+
+// the three quantisation tables as the reconstruct kernels take them (a component the file lacks: ones)
+void fill_qt(const Jpeg& j, uint16_t* qt)
+{
+    for (int c = 0; c < 3; ++c)
+        for (int i = 0; i < 64; ++i) qt[c * 64 + i] = c < j.ncomp ? j.qt[j.comp[c].tq][i] : 1;
+}
+
 }  // namespace
 
 extern "C" int editor_jpeg_parse(const uint8_t* data, long n, int* info)
@@ -1344,8 +1377,7 @@ extern "C" int editor_jpeg_entropy_decode(const uint8_t* data, long n, int16_t* 
     rc = decode(data, n, k, coef, coef_blocks);
     if (rc) return rc;
     fill_info(k, info);
-    for (int c = 0; c < 3; ++c)
-        for (int i = 0; i < 64; ++i) qt[c * 64 + i] = c < k.ncomp ? k.qt[k.comp[c].tq][i] : 1;
+    fill_qt(k, qt);
     return 0;
 }
 
@@ -1409,8 +1441,7 @@ extern "C" int editor_jpeg_plan(const uint8_t* data, long n, int* info, int* pla
     const int rc = decode(data, n, j, nullptr, 0);
     if (rc) return rc;
     fill_info(j, info);
-    for (int c = 0; c < 3; ++c)
-        for (int i = 0; i < 64; ++i) qt[c * 64 + i] = c < j.ncomp ? j.qt[j.comp[c].tq][i] : 1;
+    fill_qt(j, qt);
     memcpy(huff, sp.dht, sizeof(sp.dht));
     // one pass over the first scan's entropy-coded bytes; a byte after 0xFF is classified as BitReader::fill does: 00 is a
     // stuffed data byte, anything else (or nothing) ends the data - an RSTn ends a segment, the rest end the scan
@@ -1448,34 +1479,12 @@ extern "C" int editor_jpeg_entropy_segments(const uint8_t* bytes, long nbytes, c
 {
     if (!bytes || !fdesc || !ftab || !seg || !huff || !coef || !status) return (int)hipErrorInvalidValue;
     if (!check_entropy_tables(nbytes, fdesc, ftab, seg, nhuff, B, nseg, coef_blocks)) return (int)hipErrorInvalidValue;
-    HuffLut lut[6];
-    long done = 0;
-    for (int f = 0; f < B; ++f) {
-        status[f] = 0;
-        const long upto = ftab[(long)FT_SEGS * B + f];
-        if (upto == done) continue;
-        const int* fd = fdesc + (long)f * 16;
-        ScanGeom g;
-        make_scan_geom(fd, g);
-        for (int t = 0; t < 6; ++t)
-            if (t % 3 < g.ncomp) {
-                const uint8_t* dht = huff + (long)fd[6 + t] * DHT_BYTES;
-                lut_lengths(lut[t], dht);
-                lut_fill(lut[t], dht, 0, 1);
-            }
-        int16_t* img = coef + ftab[(long)FT_COEF * B + f] * 64;
-        memset(img, 0, (size_t)g.total_blocks * 128);
-        const long bo = ftab[(long)FT_BYTE * B + f];
-        for (long s = done; s < upto; ++s) {
-            const long m0 = seg[s * 3 + 2];
-            const long m1 = g.restart && m0 + g.restart < g.nmcu ? m0 + g.restart : g.nmcu;
-            SegState st;
-            seg_begin(st, bo + seg[s * 3], bo + seg[s * 3 + 1]);
-            st.br.buf = bytes; st.br.base = 0; st.br.lim = nbytes;
-            if (decode_segment_blocks(st, g, lut, kZigzag, img, m0, (m1 - m0) * g.bpm) != SEG_DONE) status[f] = EDITOR_JPEG_CORRUPT;
-        }
-        done = upto;
-    }
+    for_each_segment(fdesc, ftab, seg, huff, B, coef, status, [&](long, const SegDesc& d, const HuffLut* lut) {
+        SegState st;
+        seg_begin(st, d.start, d.end);
+        st.br.buf = bytes; st.br.base = 0; st.br.lim = nbytes;
+        if (decode_segment_blocks(st, d.g, lut, kZigzag, d.img, d.m0, d.nblk) != SEG_DONE) status[d.f] = EDITOR_JPEG_CORRUPT;
+    });
     return 0;
 }
 
@@ -1483,14 +1492,9 @@ extern "C" int editor_jpeg_entropy_device(const uint8_t* bytes, long nbytes, con
                                           const int* fdesc, const long* ftab, const long* seg, const uint8_t* huff, int nhuff, int B,
                                           long nseg, int16_t* coef, long coef_blocks, int* status, hipStream_t stream)
 {
-    if (!bytes || !fdesc_host || !ftab_host || !seg_host || !fdesc || !ftab || !seg || !huff || !coef || !status)
-        return (int)hipErrorInvalidValue;
-    // the kernel stages 16 bytes per lane: the byte buffer is 16-byte aligned and a whole number of such pieces
-    if (((uintptr_t)bytes & 15) || (nbytes & 15) || ((uintptr_t)coef & 15)) return (int)hipErrorInvalidValue;
-    if (!check_entropy_tables(nbytes, fdesc_host, ftab_host, seg_host, nhuff, B, nseg, coef_blocks)) return (int)hipErrorInvalidValue;
-    if (nseg > 0x7fffffffL) return (int)hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(status, 0, (size_t)B * sizeof(int), stream);
-    if (e != hipSuccess) return (int)e;
+    const int rc = entropy_device_begin(bytes, nbytes, fdesc_host, ftab_host, seg_host, fdesc, ftab, seg, huff, nhuff, B, nseg, coef, coef_blocks,
+                                        status, stream);
+    if (rc) return rc;
     if (nseg == 0) return 0;
     hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)nseg), dim3(EDITOR_WAVE), 0, stream, bytes, nbytes, fdesc, ftab, seg, huff, B, nseg,
                        coef, status);
@@ -1523,102 +1527,82 @@ extern "C" int editor_jpeg_entropy_split_segments(const uint8_t* bytes, long nby
     int* ex_s = en_s + SPLIT_LANES;
     int* cnt = ex_s + SPLIT_LANES;
     int* hit = cnt + SPLIT_LANES;                                       // (see the kernel)
-    HuffLut lut[6];
     const long chunk_bytes = (long)SPLIT_LANES * sub_bytes, budget = 8L * sub_bytes + 8;
-    long done = 0;
-    for (int f = 0; f < B; ++f) {
-        status[f] = 0;
-        const long upto = ftab[(long)FT_SEGS * B + f];
-        if (upto == done) continue;
-        const int* fd = fdesc + (long)f * 16;
-        ScanGeom g;
-        make_scan_geom(fd, g);
-        for (int t = 0; t < 6; ++t)
-            if (t % 3 < g.ncomp) {
-                const uint8_t* dht = huff + (long)fd[6 + t] * DHT_BYTES;
-                lut_lengths(lut[t], dht);
-                lut_fill(lut[t], dht, 0, 1);
+    for_each_segment(fdesc, ftab, seg, huff, B, coef, status, [&](long s, const SegDesc& d, const HuffLut* lut) {
+        const ScanGeom& g = d.g;
+        const int f = d.f;
+        const long m0 = d.m0, nblk = d.nblk, start = d.start, end = d.end;
+        int16_t* img = d.img;
+        SubCtx cx;
+        cx.g = &g; cx.lut = lut; cx.zigzag = kZigzag; cx.buf = bytes; cx.base = 0; cx.lim = nbytes; cx.end = end;
+        const long nchunks = (end - start + chunk_bytes - 1) / chunk_bytes;
+        SubState car = {start, 0};
+        long base_blk = 0, rounds = 0, chunks = 0;
+        bool bad = false;
+        // the kernel's chunk loop, its lanes one after another
+        for (long ch = 0; ch < nchunks; ++ch) {
+            if ((car.s >> 12) || base_blk >= nblk) break;
+            const long c0 = start + ch * chunk_bytes;
+            const long c1 = c0 + chunk_bytes < end ? c0 + chunk_bytes : end;
+            const long nsub = (c1 - c0 + sub_bytes - 1) / sub_bytes;
+            auto hi_of = [&](long lane) { const long lo = c0 + lane * sub_bytes; return lo + sub_bytes < end ? lo + sub_bytes : end; };
+            for (long lane = 0; lane < nsub; ++lane) {
+                SubState e = lane ? sub_guess(cx, c0 + lane * sub_bytes) : car, x = e;
+                cnt[lane] = (int)sub_walk<false>(x, cx, hi_of(lane), false, lane == 0, budget, img, m0, 0, nblk, bad);
+                hit[lane] = bad && lane > 0;
+                en_p[lane] = e.p; en_s[lane] = e.s; ex_p[lane] = x.p; ex_s[lane] = x.s;
             }
-        int16_t* img = coef + ftab[(long)FT_COEF * B + f] * 64;
-        memset(img, 0, (size_t)g.total_blocks * 128);
-        const long bo = ftab[(long)FT_BYTE * B + f];
-        for (long s = done; s < upto; ++s) {
-            const long m0 = seg[s * 3 + 2];
-            const long m1 = g.restart && m0 + g.restart < g.nmcu ? m0 + g.restart : g.nmcu;
-            const long nblk = (m1 - m0) * g.bpm;
-            const long start = bo + seg[s * 3], end = bo + seg[s * 3 + 1];
-            SubCtx cx;
-            cx.g = &g; cx.lut = lut; cx.zigzag = kZigzag; cx.buf = bytes; cx.base = 0; cx.lim = nbytes; cx.end = end;
-            const long nchunks = (end - start + chunk_bytes - 1) / chunk_bytes;
-            SubState car = {start, 0};
-            long base_blk = 0, rounds = 0, chunks = 0;
-            bool bad = false;
-            // the kernel's chunk loop, its lanes one after another
-            for (long ch = 0; ch < nchunks; ++ch) {
-                if ((car.s >> 12) || base_blk >= nblk) break;
-                const long c0 = start + ch * chunk_bytes;
-                const long c1 = c0 + chunk_bytes < end ? c0 + chunk_bytes : end;
-                const long nsub = (c1 - c0 + sub_bytes - 1) / sub_bytes;
-                auto hi_of = [&](long lane) { const long lo = c0 + lane * sub_bytes; return lo + sub_bytes < end ? lo + sub_bytes : end; };
-                for (long lane = 0; lane < nsub; ++lane) {
-                    SubState e = lane ? sub_guess(cx, c0 + lane * sub_bytes) : car, x = e;
-                    cnt[lane] = (int)sub_walk<false>(x, cx, hi_of(lane), false, lane == 0, budget, img, m0, 0, nblk, bad);
-                    hit[lane] = bad && lane > 0;
-                    en_p[lane] = e.p; en_s[lane] = e.s; ex_p[lane] = x.p; ex_s[lane] = x.s;
+            ++rounds;
+            for (long r = 1; r < nsub; ++r) {
+                bool any = false;
+                for (long lane = nsub - 1; lane > 0; --lane) {         // (downwards: lane - 1 still holds the last round's exit)
+                    const SubState ne = {ex_p[lane - 1], ex_s[lane - 1]}, e = {en_p[lane], en_s[lane]};
+                    any = any || hit[lane];
+                    if (!sub_differs(ne, e) && !(hit[lane] && lane <= r)) continue;
+                    any = true;
+                    SubState x = ne;
+                    cnt[lane] = (int)sub_walk<false>(x, cx, hi_of(lane), false, lane <= r, budget, img, m0, 0, nblk, bad);
+                    hit[lane] = bad && lane > r;
+                    en_p[lane] = ne.p; en_s[lane] = ne.s; ex_p[lane] = x.p; ex_s[lane] = x.s;
                 }
+                if (!any) break;
                 ++rounds;
-                for (long r = 1; r < nsub; ++r) {
-                    bool any = false;
-                    for (long lane = nsub - 1; lane > 0; --lane) {         // (downwards: lane - 1 still holds the last round's exit)
-                        const SubState ne = {ex_p[lane - 1], ex_s[lane - 1]}, e = {en_p[lane], en_s[lane]};
-                        any = any || hit[lane];
-                        if (!sub_differs(ne, e) && !(hit[lane] && lane <= r)) continue;
-                        any = true;
-                        SubState x = ne;
-                        cnt[lane] = (int)sub_walk<false>(x, cx, hi_of(lane), false, lane <= r, budget, img, m0, 0, nblk, bad);
-                        hit[lane] = bad && lane > r;
-                        en_p[lane] = ne.p; en_s[lane] = ne.s; ex_p[lane] = x.p; ex_s[lane] = x.s;
-                    }
-                    if (!any) break;
-                    ++rounds;
-                }
-                long first = base_blk;
-                for (long lane = 0; lane < nsub; ++lane) {
-                    SubState t = {en_p[lane], en_s[lane]};
-                    bool lane_bad = false;
-                    sub_walk<true>(t, cx, hi_of(lane), false, true, budget, img, m0, first, nblk, lane_bad);
-                    if (lane_bad) status[f] = EDITOR_JPEG_CORRUPT;
-                    first += cnt[lane];
-                }
-                car.p = ex_p[nsub - 1]; car.s = ex_s[nsub - 1]; base_blk = first;
-                ++chunks;
             }
-            if (!((car.s >> 12) & SUB_ERR) && base_blk < nblk) {
-                SubCtx tc = cx;
-                tc.base = 0; tc.lim = 0;
-                SubState t = {car.p, car.s & ~7};
-                bool tail_bad = false;
-                sub_walk<true>(t, tc, 0, true, true, (nblk - base_blk) * 64 + 64, img, m0, base_blk, nblk, tail_bad);
-                if (tail_bad) status[f] = EDITOR_JPEG_CORRUPT;
+            long first = base_blk;
+            for (long lane = 0; lane < nsub; ++lane) {
+                SubState t = {en_p[lane], en_s[lane]};
+                bool lane_bad = false;
+                sub_walk<true>(t, cx, hi_of(lane), false, true, budget, img, m0, first, nblk, lane_bad);
+                if (lane_bad) status[f] = EDITOR_JPEG_CORRUPT;
+                first += cnt[lane];
             }
-            const long per = (nblk + SPLIT_LANES - 1) / SPLIT_LANES;
-            uint32_t pred[3] = {0, 0, 0};
-            uint32_t sums[SPLIT_LANES][3];
-            for (long lane = 0; lane < SPLIT_LANES; ++lane) {
-                const long b0 = lane * per < nblk ? lane * per : nblk, b1 = b0 + per < nblk ? b0 + per : nblk;
-                sums[lane][0] = sums[lane][1] = sums[lane][2] = 0;
-                dc_lane_sum(g, img, m0, b0, b1, sums[lane]);
-            }
-            for (long lane = 0; lane < SPLIT_LANES; ++lane) {
-                const long b0 = lane * per < nblk ? lane * per : nblk, b1 = b0 + per < nblk ? b0 + per : nblk;
-                uint32_t mine[3] = {pred[0], pred[1], pred[2]};           // the exclusive prefix sum of the lanes' sums
-                dc_lane_apply(g, img, m0, b0, b1, mine);
-                for (int c = 0; c < 3; ++c) pred[c] += sums[lane][c];
-            }
-            stats[s * 2] = rounds; stats[s * 2 + 1] = chunks;
+            car.p = ex_p[nsub - 1]; car.s = ex_s[nsub - 1]; base_blk = first;
+            ++chunks;
         }
-        done = upto;
-    }
+        if (!((car.s >> 12) & SUB_ERR) && base_blk < nblk) {
+            SubCtx tc = cx;
+            tc.base = 0; tc.lim = 0;
+            SubState t = {car.p, car.s & ~7};
+            bool tail_bad = false;
+            sub_walk<true>(t, tc, 0, true, true, (nblk - base_blk) * 64 + 64, img, m0, base_blk, nblk, tail_bad);
+            if (tail_bad) status[f] = EDITOR_JPEG_CORRUPT;
+        }
+        const long per = (nblk + SPLIT_LANES - 1) / SPLIT_LANES;
+        uint32_t pred[3] = {0, 0, 0};
+        uint32_t sums[SPLIT_LANES][3];
+        for (long lane = 0; lane < SPLIT_LANES; ++lane) {
+            const long b0 = lane * per < nblk ? lane * per : nblk, b1 = b0 + per < nblk ? b0 + per : nblk;
+            sums[lane][0] = sums[lane][1] = sums[lane][2] = 0;
+            dc_lane_sum(g, img, m0, b0, b1, sums[lane]);
+        }
+        for (long lane = 0; lane < SPLIT_LANES; ++lane) {
+            const long b0 = lane * per < nblk ? lane * per : nblk, b1 = b0 + per < nblk ? b0 + per : nblk;
+            uint32_t mine[3] = {pred[0], pred[1], pred[2]};           // the exclusive prefix sum of the lanes' sums
+            dc_lane_apply(g, img, m0, b0, b1, mine);
+            for (int c = 0; c < 3; ++c) pred[c] += sums[lane][c];
+        }
+        stats[s * 2] = rounds; stats[s * 2 + 1] = chunks;
+    });
     return 0;
 }
 
@@ -1627,14 +1611,11 @@ extern "C" int editor_jpeg_entropy_split_device(const uint8_t* bytes, long nbyte
                                                 int nhuff, int B, long nseg, int sub_bytes, void* workspace, long workspace_bytes, int16_t* coef,
                                                 long coef_blocks, int* status, hipStream_t stream)
 {
-    if (!bytes || !fdesc_host || !ftab_host || !seg_host || !fdesc || !ftab || !seg || !huff || !workspace || !coef || !status)
-        return (int)hipErrorInvalidValue;
-    if (((uintptr_t)bytes & 15) || (nbytes & 15) || ((uintptr_t)coef & 15)) return (int)hipErrorInvalidValue;      // as editor_jpeg_entropy_device
     long ws = 0;
-    if (editor_jpeg_entropy_split_workspace(nseg, sub_bytes, &ws) || workspace_bytes < ws || ((uintptr_t)workspace & 7)) return (int)hipErrorInvalidValue;
-    if (!check_entropy_tables(nbytes, fdesc_host, ftab_host, seg_host, nhuff, B, nseg, coef_blocks)) return (int)hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(status, 0, (size_t)B * sizeof(int), stream);
-    if (e != hipSuccess) return (int)e;
+    if (!workspace || editor_jpeg_entropy_split_workspace(nseg, sub_bytes, &ws) || workspace_bytes < ws || ((uintptr_t)workspace & 7)) return (int)hipErrorInvalidValue;
+    const int rc = entropy_device_begin(bytes, nbytes, fdesc_host, ftab_host, seg_host, fdesc, ftab, seg, huff, nhuff, B, nseg, coef, coef_blocks,
+                                        status, stream);
+    if (rc) return rc;
     if (nseg == 0) return 0;
     const size_t lds = (size_t)split_window_bytes(sub_bytes) + SPLIT_LDS_FIXED;
     hipLaunchKernelGGL(jpeg_entropy_split_kernel, dim3((unsigned)nseg), dim3(SPLIT_LANES), lds, stream, bytes, nbytes, fdesc, ftab, seg, huff, B,

@@ -451,7 +451,7 @@ class DeviceJpegDecoder:
         self.crop_w = int(crop_w)
         self._cd = _lib.lib().cdll
         self._pool = ThreadPoolExecutor(max_workers=max(1, int(threads)))
-        self._arena, self._h2d_done = None, None            # decode_ragged's pinned staging buffer and its last copy's event
+        self._arena, self._h2d_done = None, None            # the pinned staging buffer (_stage) and its last copy's event
 
     @staticmethod
     def _refusal(rc):
@@ -545,76 +545,122 @@ class DeviceJpegDecoder:
         spans = list(zip(e_idx.tolist(), pos.tolist(), s0.tolist(), e1.tolist()))
         return nbytes, spans, fdesc, ftab, segs, huff, nseg
 
-    def _device_entropy(self, files, bp, coef_d, block_off, device, extra=()):
-        """Fills coef_d (flat int16 device tensor) at block_off[i] for every file of the planned batch: ONE host-to-device copy
-        of the eligible files' scan bytes + descriptor tables (+ the caller's `extra` arrays) and one launch of
-        editor_jpeg_entropy_device (entropy="device_split": editor_jpeg_entropy_split_device); a host-routed file is decoded by editor_jpeg_entropy_decode on the pool and its range copied
-        (one copy per such file).  -> (status tensor, device views of extra)."""
+    # ---- the pipeline: describe the batch, fill its coefficients, reconstruct ----------------------------------------------
+    @staticmethod
+    def _cuda(device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("DeviceJpegDecoder reconstructs on the GPU (no CPU fallback)")
+        return device
+
+    def _describe(self, files):
+        """Every file parsed before anything is launched -> (infos (B,16) int32, JpegBatchPlan or None): entropy="host" runs
+        editor_jpeg_parse on the pool (the planner is single-threaded), the device modes plan.  A file the parser refuses raises
+        ValueError naming its index in the batch."""
+        if self.entropy != "host":
+            bp = self.plan_batch(files)
+            return bp.infos, bp
+        infos = np.zeros((len(files), 16), dtype=np.int32)
+        for i, rc in enumerate(self._pool.map(lambda i: self._parse_rc(files[i], infos[i]), range(len(files)))):
+            if rc:
+                raise ValueError("file %d of the batch: %s" % (i, self._refusal(rc)))
+        return infos, None
+
+    def _stage(self, nbytes):
+        """The pinned staging buffer: grow-only and reused across calls (pinning per call costs more than the copy it speeds
+        up), so the previous call's host-to-device copies must have left it before it is written again."""
+        if self._h2d_done is not None:
+            self._h2d_done.synchronize()
+        if self._arena is None or self._arena.numel() < nbytes:
+            self._arena = torch.empty(max(nbytes, 2 * (self._arena.numel() if self._arena is not None else 0)), dtype=torch.uint8).pin_memory()
+        return self._arena
+
+    def _coefficients(self, files, infos, bp, order, device, extra=()):
+        """The coefficient tensor of a described batch: flat int16 on the device, the files' blocks one after another in `order`.
+        bp None (entropy="host"): every file is host-routed - decoded by editor_jpeg_entropy_decode on the pool, straight into
+        the staging buffer.  Otherwise the plan's eligible files travel as scan bytes and one launch of editor_jpeg_entropy_device
+        (entropy="device_split": editor_jpeg_entropy_split_device) decodes them; the rest are host-routed as above.  Staged as
+        scan bytes | 16-byte-aligned tables (the entropy kernel's four, the quantisation tables in `order`, the caller's `extra`) |
+        host-routed coefficients in `order`: ONE copy for bytes and tables, one per run of host-routed files adjacent in the
+        tensor.  -> (coef_d, block_off, status tensor or None, quantisation tables (B*192 int16, uint16 bit patterns), device
+        views of extra)."""
         b = len(files)
-        nbytes, spans, fdesc, ftab, segs, huff, nseg = self.pack_batch(files, bp, block_off)
-        h_idx = np.nonzero(bp.plans[:, 0] == 0)[0].tolist()
-        parts = [fdesc, ftab, segs, huff] + [np.ascontiguousarray(a) for a in extra]
+        order = np.asarray(order, dtype=np.int64)
+        blocks = infos[:, 8].astype(np.int64)
+        block_off = np.zeros(b, dtype=np.int64)
+        block_off[order] = np.cumsum(blocks[order]) - blocks[order]
+        nblocks = int(blocks.sum())
+        if bp is None:
+            nbytes, spans, tables, hosted = 0, [], [], np.ones(b, dtype=bool)
+        else:
+            nbytes, spans, fdesc, ftab, segs, huff, nseg = self.pack_batch(files, bp, block_off)
+            tables, hosted = [fdesc, ftab, segs, huff], bp.plans[:, 0] == 0
+        parts = tables + [np.zeros((b, 192), dtype=np.uint16) if bp is None else bp.qts[order]] + [np.ascontiguousarray(a) for a in extra]
         offs, o = [], nbytes
         for a in parts:
             offs.append(o)
             o += (a.nbytes + 15) & ~15
         blob = o
-        h_off = []
-        for i in h_idx:
-            h_off.append(o)
-            o += int(bp.infos[i, 8]) * 128
+        ho = order[hosted[order]]                             # the host-routed files as they lie in the tensor
+        hb = blocks[ho]
+        c_off, q_off = np.zeros(b, dtype=np.int64), np.zeros(b, dtype=np.int64)
+        c_off[ho] = blob + 128 * (np.cumsum(hb) - hb)
+        q_off[order] = offs[len(tables)] + 384 * np.arange(b)
+        o += 128 * int(hb.sum())
         arena = self._stage(o)
         host = arena.numpy()
         for i, at, s0, e1 in spans:
             host[at:at + e1 - s0] = np.frombuffer(files[i], dtype=np.uint8)[s0:e1]
         for a, at in zip(parts, offs):
             host[at:at + a.nbytes] = a.reshape(-1).view(np.uint8)
-        if h_idx:
-            base = arena.data_ptr()
-            sq, si = np.zeros((len(h_idx), 192), dtype=np.uint16), np.zeros((len(h_idx), 16), dtype=np.int32)
+        base = arena.data_ptr()
+        scratch = np.zeros((b, 16), dtype=np.int32)
 
-            def entropy(j):
-                try:
-                    self._entropy(files[h_idx[j]], base + h_off[j], int(bp.infos[h_idx[j], 8]), sq[j].ctypes.data, si[j])
-                except ValueError as e:
-                    raise ValueError("file %d of the batch: %s" % (h_idx[j], e)) from None
-            list(self._pool.map(entropy, range(len(h_idx))))
-        coef_blocks = coef_d.numel() // 64
+        def entropy(i):                                       # (its quantisation tables land on the plan's copy of the same values)
+            try:
+                self._entropy(files[i], base + int(c_off[i]), int(blocks[i]), base + int(q_off[i]), scratch[i])
+            except ValueError as e:
+                raise ValueError("file %d of the batch: %s" % (i, e)) from None
+        list(self._pool.map(entropy, np.nonzero(hosted)[0].tolist()))
+        runs = np.nonzero(np.concatenate([[True], block_off[ho[1:]] != block_off[ho[:-1]] + hb[:-1]]))[0].tolist() if len(ho) else []
         with torch.cuda.device(device):
+            coef_d = torch.empty(nblocks * 64, dtype=torch.int16, device=device)
             blob_d = torch.empty(blob, dtype=torch.uint8, device=device)
             blob_d.copy_(arena[:blob], non_blocking=True)
-            for j, i in enumerate(h_idx):
-                n16 = int(bp.infos[i, 8]) * 64
-                coef_d[int(block_off[i]) * 64:int(block_off[i]) * 64 + n16].copy_(arena[h_off[j]:h_off[j] + 2 * n16].view(torch.int16), non_blocking=True)
+            for r0, r1 in zip(runs, runs[1:] + [len(ho)]):
+                src, dst, n16 = int(c_off[ho[r0]]), int(block_off[ho[r0]]) * 64, int(hb[r0:r1].sum()) * 64
+                coef_d[dst:dst + n16].copy_(arena[src:src + 2 * n16].view(torch.int16), non_blocking=True)
             self._h2d_done = torch.cuda.Event()
             self._h2d_done.record()
             self.last_h2d_bytes = o
             dev = [blob_d[at:at + a.nbytes] for a, at in zip(parts, offs)]
-            status = torch.empty(b, dtype=torch.int32, device=device)
-            tables = (blob_d[:nbytes], nbytes, ctypes.c_void_p(fdesc.ctypes.data), ctypes.c_void_p(ftab.ctypes.data),
-                      ctypes.c_void_p(segs.ctypes.data), dev[0].view(torch.int32), dev[1].view(torch.int64), dev[2].view(torch.int64), dev[3],
-                      int(huff.shape[0]), b, nseg)
-            if self.entropy == "device_split":
-                ws = ctypes.c_long(0)
-                if self._cd.editor_jpeg_entropy_split_workspace(nseg, self.split_sub_bytes, ctypes.byref(ws)):
-                    raise RuntimeError("editor_jpeg_entropy_split_workspace refused %d segments" % nseg)
-                work = torch.empty(ws.value // 8, dtype=torch.int64, device=device)
-                call("editor_jpeg_entropy_split_device", *tables, self.split_sub_bytes, work, ws.value, coef_d, coef_blocks, status)
-            else:
-                call("editor_jpeg_entropy_device", *tables, coef_d, coef_blocks, status)
-        return status, dev[4:]
+            status = None
+            if bp is not None:
+                status = torch.empty(b, dtype=torch.int32, device=device)
+                args = (blob_d[:nbytes], nbytes, ctypes.c_void_p(fdesc.ctypes.data), ctypes.c_void_p(ftab.ctypes.data),
+                        ctypes.c_void_p(segs.ctypes.data), dev[0].view(torch.int32), dev[1].view(torch.int64), dev[2].view(torch.int64), dev[3],
+                        int(huff.shape[0]), b, nseg)
+                if self.entropy == "device_split":
+                    ws = ctypes.c_long(0)
+                    if self._cd.editor_jpeg_entropy_split_workspace(nseg, self.split_sub_bytes, ctypes.byref(ws)):
+                        raise RuntimeError("editor_jpeg_entropy_split_workspace refused %d segments" % nseg)
+                    work = torch.empty(ws.value // 8, dtype=torch.int64, device=device)
+                    call("editor_jpeg_entropy_split_device", *args, self.split_sub_bytes, work, ws.value, coef_d, nblocks, status)
+                else:
+                    call("editor_jpeg_entropy_device", *args, coef_d, nblocks, status)
+        return coef_d, block_off, status, dev[len(tables)].view(torch.int16), dev[len(tables) + 1:]
 
     @staticmethod
     def _raise_status(status):
         """Reads the kernel's per-file status back (a synchronisation): corrupt entropy data is reported AFTER the launch."""
-        bad = torch.nonzero(status).flatten().tolist()
+        bad = torch.nonzero(status).flatten().tolist() if status is not None else []
         if bad:
             raise ValueError("file %d of the batch: JPEG entropy decode failed (rc %d)" % (bad[0], int(status[bad[0]])))
 
-    def _call_device(self, files, device):
+    def __call__(self, files, device):
+        device = self._cuda(device)
         files = list(files)
-        bp = self.plan_batch(files)
-        infos = bp.infos
+        infos, bp = self._describe(files)
         w, h = int(infos[0][0]), int(infos[0][1])
         cw = self.crop_w if self.crop_w > 0 else w
         ncrop = w // cw
@@ -622,18 +668,11 @@ class DeviceJpegDecoder:
             raise ValueError("DeviceJpegDecoder: the files of a batch must share one image size >= the crop width")
         b = len(files)
         groups = {}
-        for i, inf in enumerate(infos):                      # one reconstruct call per coefficient geometry; ONE entropy launch
+        for i, inf in enumerate(infos):                      # one reconstruct call per coefficient geometry (sampling factors)
             groups.setdefault(tuple(int(v) for v in inf[:9]), []).append(i)
-        order = [i for idx in groups.values() for i in idx]
-        block_off = np.zeros(b, dtype=np.int64)
-        blocks = infos[order, 8].astype(np.int64)
-        block_off[order] = np.cumsum(blocks) - blocks        # file j of a group sits at the group's start + j * blocks_per_image
-        total = int(blocks.sum())
-        with torch.cuda.device(device):
-            coef_d = torch.empty(total * 64, dtype=torch.int16, device=device)
-            out = torch.empty(ncrop, b, h, cw, 3, dtype=torch.uint8, device=device)
-        status, (qt_d,) = self._device_entropy(files, bp, coef_d, block_off, device, extra=[bp.qts[order]])
-        qt_d = qt_d.view(torch.int16)
+        order = [i for idx in groups.values() for i in idx]  # file j of a group sits at the group's start + j * blocks_per_image
+        coef_d, block_off, status, qt_d, _ = self._coefficients(files, infos, bp, order, device)
+        out = torch.empty(ncrop, b, h, cw, 3, dtype=torch.uint8, device=device)
         at = 0
         for key, idx in groups.items():
             n, nb = len(idx), key[8]
@@ -651,118 +690,27 @@ class DeviceJpegDecoder:
         self._raise_status(status)
         return out
 
-    def _decode_ragged_device(self, files, device):
-        b = len(files)
-        bp = self.plan_batch(files)
-        infos = bp.infos
-        tab, nblocks, npixels = ragged_decode_plan(infos)
-        with torch.cuda.device(device):
-            coef_d = torch.empty(nblocks * 64, dtype=torch.int16, device=device)
-        status, (qt_d, info_d, tab_d) = self._device_entropy(files, bp, coef_d, tab[0], device, extra=[bp.qts, infos, tab])
-        with torch.cuda.device(device):
-            planes = torch.empty(nblocks * 64, dtype=torch.uint8, device=device)
-            data = torch.empty(npixels * 3, dtype=torch.uint8, device=device)
-            call("editor_jpeg_reconstruct_ragged", coef_d, qt_d.view(torch.int16), ctypes.c_void_p(infos.ctypes.data), ctypes.c_void_p(tab.ctypes.data),
-                 info_d.view(torch.int32), tab_d.view(torch.int64), b, planes, data)
-        self._raise_status(status)
-        offsets = np.concatenate([tab[2], [npixels * 3]]).astype(np.int64)
-        sizes = np.ascontiguousarray(infos[:, [1, 0]])
-        return RaggedImages(data, torch.from_numpy(offsets), torch.from_numpy(sizes))
-
-    def __call__(self, files, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("DeviceJpegDecoder reconstructs on the GPU (no CPU fallback)")
-        if self.entropy != "host":
-            return self._call_device(files, device)
-        infos = [self.parse(f) for f in files]
-        w, h = int(infos[0][0]), int(infos[0][1])
-        cw = self.crop_w if self.crop_w > 0 else w
-        ncrop = w // cw
-        if ncrop < 1 or any(int(i[0]) != w or int(i[1]) != h for i in infos):
-            raise ValueError("DeviceJpegDecoder: the files of a batch must share one image size >= the crop width")
-        b = len(files)
-        out = torch.empty(ncrop, b, h, cw, 3, dtype=torch.uint8, device=device)
-        groups = {}
-        for i, inf in enumerate(infos):                      # one launch per coefficient geometry (sampling factors)
-            groups.setdefault(tuple(int(v) for v in inf[:9]), []).append(i)
-        for key, idx in groups.items():
-            blocks = key[8]
-            n = len(idx)
-            coef = torch.empty(n, blocks, 64, dtype=torch.int16).pin_memory()
-            qt = torch.empty(n, 3, 64, dtype=torch.int16).pin_memory()           # (uint16 bit patterns)
-            ginfo = [np.zeros(16, dtype=np.int32) for _ in idx]
-            list(self._pool.map(lambda a: self._entropy(files[a[1]], coef[a[0]].data_ptr(), blocks, qt[a[0]].data_ptr(), ginfo[a[0]]),
-                                enumerate(idx)))
-            pb = ctypes.c_long(0)
-            self._cd.editor_jpeg_planes_bytes(ctypes.c_void_p(ginfo[0].ctypes.data), ctypes.byref(pb))
-            coef_d, qt_d = coef.to(device, non_blocking=True), qt.to(device, non_blocking=True)
-            planes = torch.empty(n * pb.value, dtype=torch.uint8, device=device)
-            dst = out if n == b else torch.empty(ncrop, n, h, cw, 3, dtype=torch.uint8, device=device)
-            call("editor_jpeg_reconstruct", coef_d, qt_d, ctypes.c_void_p(ginfo[0].ctypes.data), n, planes, cw, dst)
-            if n != b:
-                out[:, torch.tensor(idx, device=device)] = dst
-        return out
-
-    def _stage(self, nbytes):
-        """The pinned staging buffer of decode_ragged: grow-only and reused across calls (pinning per call costs more than the
-        copy it speeds up), so the previous call's host-to-device copies must have left it before it is written again."""
-        if self._h2d_done is not None:
-            self._h2d_done.synchronize()
-        if self._arena is None or self._arena.numel() < nbytes:
-            self._arena = torch.empty(max(nbytes, 2 * (self._arena.numel() if self._arena is not None else 0)), dtype=torch.uint8).pin_memory()
-        return self._arena
-
     def decode_ragged(self, files, device):
         """A batch of JPEG files of ANY mix of sizes / sampling factors / grayscale / baseline / progressive -> RaggedImages
         (grayscale replicated to three channels, as `convert('RGB')` does).  Every file is parsed before anything is launched: a
-        corrupt or unsupported one raises ValueError naming its index in the batch.  Then the thread pool Huffman-decodes each
-        file into the staging buffer at the file's block offset, three host-to-device copies (coefficients, quantisation tables,
-        descriptor table) and ONE call of the ragged entry: two launches per batch, whatever the sizes.  With entropy="device"
-        (class docstring) the files are planned instead, one copy carries scan bytes and tables, and a third launch decodes them."""
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("DeviceJpegDecoder reconstructs on the GPU (no CPU fallback)")
+        corrupt or unsupported one raises ValueError naming its index in the batch.  Then _coefficients fills the coefficient
+        tensor (entropy="host": the pool Huffman-decodes into the staging buffer, two host-to-device copies; the device modes:
+        class docstring) and ONE call of the ragged entry reconstructs: two launches per batch, whatever the sizes, three with
+        the entropy kernel."""
+        device = self._cuda(device)
         files = list(files)
         b = len(files)
         if b < 1:
             raise ValueError("DeviceJpegDecoder.decode_ragged: empty batch")
-        if self.entropy != "host":
-            return self._decode_ragged_device(files, device)
-        infos = np.zeros((b, 16), dtype=np.int32)
-        for i, rc in enumerate(self._pool.map(lambda i: self._parse_rc(files[i], infos[i]), range(b))):
-            if rc:
-                raise ValueError("file %d of the batch: %s" % (i, self._refusal(rc)))
+        infos, bp = self._describe(files)
         tab, nblocks, npixels = ragged_decode_plan(infos)
-        n_coef, n_qt, n_info = nblocks * 128, b * 384, b * 64                    # bytes; every region starts 8-byte aligned
-        arena = self._stage(n_coef + n_qt + n_info + tab.nbytes)
-        base = arena.data_ptr()
-        host = arena.numpy()
-        scratch = np.zeros((b, 16), dtype=np.int32)
-
-        def entropy(i):
-            try:
-                self._entropy(files[i], base + int(tab[0, i]) * 128, int(infos[i, 8]), base + n_coef + i * 384, scratch[i])
-            except ValueError as e:
-                raise ValueError("file %d of the batch: %s" % (i, e)) from None
-        list(self._pool.map(entropy, range(b)))
-        o_tab = n_coef + n_qt + n_info
-        host[n_coef + n_qt:o_tab] = infos.reshape(-1).view(np.uint8)
-        host[o_tab:o_tab + tab.nbytes] = tab.reshape(-1).view(np.uint8)
+        coef_d, _, status, qt_d, (info_d, tab_d) = self._coefficients(files, infos, bp, range(b), device, extra=[infos, tab])
         with torch.cuda.device(device):
-            coef_d = torch.empty(nblocks * 64, dtype=torch.int16, device=device)
-            qt_d = torch.empty(b * 192, dtype=torch.int16, device=device)        # (uint16 bit patterns)
-            desc_d = torch.empty(n_info + tab.nbytes, dtype=torch.uint8, device=device)
-            coef_d.copy_(arena[:n_coef].view(torch.int16), non_blocking=True)
-            qt_d.copy_(arena[n_coef:n_coef + n_qt].view(torch.int16), non_blocking=True)
-            desc_d.copy_(arena[n_coef + n_qt:o_tab + tab.nbytes], non_blocking=True)
-            self._h2d_done = torch.cuda.Event()
-            self._h2d_done.record()
-            self.last_h2d_bytes = o_tab + tab.nbytes
             planes = torch.empty(nblocks * 64, dtype=torch.uint8, device=device)
             data = torch.empty(npixels * 3, dtype=torch.uint8, device=device)
             call("editor_jpeg_reconstruct_ragged", coef_d, qt_d, ctypes.c_void_p(infos.ctypes.data), ctypes.c_void_p(tab.ctypes.data),
-                 desc_d[:n_info].view(torch.int32), desc_d[n_info:].view(torch.int64), b, planes, data)
+                 info_d.view(torch.int32), tab_d.view(torch.int64), b, planes, data)
+        self._raise_status(status)
         offsets = np.concatenate([tab[2], [npixels * 3]]).astype(np.int64)
         sizes = np.ascontiguousarray(infos[:, [1, 0]])
         return RaggedImages(data, torch.from_numpy(offsets), torch.from_numpy(sizes))
@@ -784,7 +732,7 @@ def load_modalities(files_by_modality, size, interpolation=3, device="cuda", ent
     b = len(groups[0])
     if any(len(g) != b for g in groups):
         raise ValueError("load_modalities: every modality lists the same number of files")
-    dkey = "decoder" if entropy == "host" else ("decoder", entropy)
+    dkey = ("decoder", entropy)
     dec = _DEFAULT.get(dkey)
     if dec is None:
         dec = _DEFAULT[dkey] = DeviceJpegDecoder(crop_w=0, threads=16, entropy=entropy)

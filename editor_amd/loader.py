@@ -151,18 +151,9 @@ class DeviceBatchLoader:
     def _refused(self, err, dec, files, paths):
         """ValueError of the decoder -> ValueError naming the file's path and its index in the batch."""
         m = re.search(r"file (\d+) of the batch: (.*)", str(err))
-        if m:
-            at, why = int(m.group(1)), m.group(2)
-        else:                                                 # (the uniform host path parses file after file and names none)
-            at, why = None, str(err)
-            for i, f in enumerate(files):
-                try:
-                    dec.parse(f)
-                except ValueError:
-                    at = i
-                    break
-        if at is None:
+        if not m:
             return err
+        at, why = int(m.group(1)), m.group(2)
         return ValueError("%s (file %d of the batch): %s" % (paths[at], at, why))
 
     def _make(self, idx, draws):

@@ -142,7 +142,9 @@ __global__ __launch_bounds__(256) void split_multi_kernel(const float* const* __
     }
     for (long i = (n & ~3L) + threadIdx.x; i < n; i += 256) {
         const float v = p[i] * scale;
-        const uint16_t h = f32_to_f16(v);
+        // (the compiler folds product and conversion into v_fma_mixlo_f16(p, scale, +0), which turns -0 into +0: v's sign is OR-ed
+        // back in, so that the tail writes the bits of the 16-byte body above - half(-0) = 0x8000)
+        const uint16_t h = f32_to_f16(v) | (uint16_t)((__float_as_uint(v) >> 16) & 0x8000u);
         hi[i] = h; lo[i] = f32_to_f16(v - f16_to_f32(h));
     }
 }

@@ -594,7 +594,7 @@ int editor_resize_u8_ragged(const uint8_t* in, int B, int Hout, int Wout, const 
 
 /* torch.optim.SGD(momentum, weight_decay, dampening 0) over many tensors in one launch.  Pointer tables and per-tensor
  * lr / wd live in device memory; chunk c covers elements [chunk_off[c], +editor_sgd_chunk_elems()) of tensor chunk_tensor[c].
- * g_ptrs[t] == NULL skips tensor t.  first != 0: momentum buffers are initialised with the (decayed) gradient.
+ * g_ptrs[t] == NULL skips tensor t: its parameter, momentum buffer and shadow are left as they are.
  * h_ptrs (optional table, entries may be NULL): 16-bit shadow of the updated tensor - the GEMM operand copy - written in
  * the same pass instead of by one cast launch per weight; shadow_dtype: 1 = bf16, 2 = f16.
  * Momentum buffers must start at zero: mu*0 + g' reproduces torch's first-step `buf = g'` exactly (no "first" flag that

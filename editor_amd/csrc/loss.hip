@@ -1,8 +1,9 @@
 // Loss head that consumes the hot path's outputs, gfx950.  Tiny, latency-bound kernels
 // (B x num_classes, B x 2304) whose job is to keep the whole training step inside libeditor_hip.so.
 //   CrossEntropyLabelSmooth(eps)        layers/softmax_loss.py:4-34
-//   TripletLoss() soft-margin form      layers/triplet_loss.py:16-33 (euclidean_dist), 51-84 (hard_example_mining),
-//                                       121-136 (SoftMarginLoss(dist_an - dist_ap, 1))
+//   TripletLoss(margin, hard_factor)    layers/triplet_loss.py:16-33 (euclidean_dist), 51-84 (hard_example_mining),
+//                                       121-136 (SoftMarginLoss(dist_an - dist_ap, 1) or MarginRankingLoss(margin)),
+//                                       5-13 (normalize, for normalize_feature=True)
 // Every reduction runs in a fixed order (no atomics): the loss and its gradients are run-to-run deterministic.
 #include "common.h"
 #include "../../include/editor_hip.h"
@@ -84,14 +85,19 @@ __global__ void row_sqnorm_kernel(const float* __restrict__ f, long ldf, int D, 
 
 // one block per anchor: hardest positive (max distance among equal labels, self included as in the reference) and
 // hardest negative (min among different labels).  Ties resolve to the lowest index.
-// coef[i] = sigmoid(d_ap - d_an); coef[B+i] = 1/d_ap (0 where clamped); coef[2B+i] = 1/d_an.
+// With z = (1+hf) d_ap - (1-hf) d_an (hf = hard_factor, triplet_loss.py:128-129):
+//   form 0 (SoftMarginLoss):     row_loss = softplus(z),      coef[i] = sigmoid(z)
+//   form 1 (MarginRankingLoss):  row_loss = max(z + margin, 0), coef[i] = [z + margin >= 0] (clamp_min passes at equality)
+// coef[B+i] = (1+hf)/d_ap (0 where clamped); coef[2B+i] = (1-hf)/d_an: the backward kernel serves every form unchanged.
+// dist (2B, may be NULL): the scaled distances (1+hf) d_ap, (1-hf) d_an the reference returns.  hf = 0 multiplies by exactly 1.
 // Non-finite features (an overflowed f16 step): torch.clamp keeps a NaN and torch.max / torch.min return it, so an anchor with
 // a NaN distance among its positives (negatives) has d_ap (d_an) = NaN and a NaN loss; fmaxf alone would turn that distance
 // into 1e-6.  A NaN never wins the ordered comparisons of the search, so the indices come from the comparable distances only:
 // idx[i] (positive) always lies in [0, B) - it falls back to the anchor itself, which is its own positive, when every positive
 // distance is NaN - and idx[B+i] (negative) in [-1, B), -1 = no comparable negative (the backward skips that term).
 __global__ void triplet_mine_kernel(const float* __restrict__ gram, const float* __restrict__ sq,
-    const long* __restrict__ label, int B, int* __restrict__ idx, float* __restrict__ coef, float* __restrict__ row_loss)
+    const long* __restrict__ label, int B, int form, float margin, float hf, int* __restrict__ idx, float* __restrict__ coef,
+    float* __restrict__ row_loss, float* __restrict__ dist)
 {
     __shared__ float sv[2][256];
     __shared__ int si[2][256];
@@ -125,13 +131,22 @@ __global__ void triplet_mine_kernel(const float* __restrict__ gram, const float*
         const float ap = (nan_any & 1) ? NAN : sv[0][0], an = (nan_any & 2) ? NAN : sv[1][0];
         const int p = si[0][0] >= 0 ? si[0][0] : i, n = si[1][0];
         idx[i] = p; idx[B + i] = n;
-        const float z = ap - an;                                         // SoftMarginLoss(an - ap, 1) = log(1 + e^z)
-        row_loss[i] = z > 0.f ? z + log1pf(expf(-z)) : log1pf(expf(z));
-        coef[i] = 1.f / (1.f + expf(-z));
+        const float sp = 1.f + hf, sn = 1.f - hf;
+        const float dp = __fmul_rn(sp, ap), dn = __fmul_rn(sn, an);     // (rounded products, as the reference's in-place scaling)
+        if (dist) { dist[i] = dp; dist[B + i] = dn; }
+        const float z = dp - dn;
+        if (form == 0) {                                                 // SoftMarginLoss(an - ap, 1) = log(1 + e^z)
+            row_loss[i] = z > 0.f ? z + log1pf(expf(-z)) : log1pf(expf(z));
+            coef[i] = 1.f / (1.f + expf(-z));
+        } else {                                                         // MarginRankingLoss: a NaN z stays NaN in the loss AND in
+            const float h = z + margin;                                  // coef (fmaxf(h, 0) would return 0 and hide the overflow)
+            row_loss[i] = h != h ? h : fmaxf(h, 0.f);
+            coef[i] = h != h ? h : (h >= 0.f ? 1.f : 0.f);
+        }
         const float qp = sqi + sq[p] - 2.f * gram[(long)i * B + p];
         const float qn = n >= 0 ? sqi + sq[n] - 2.f * gram[(long)i * B + n] : 0.f;
-        coef[B + i] = qp > 1e-12f ? 1.f / ap : 0.f;                      // clamp(min) passes no gradient below the floor
-        coef[2 * B + i] = (n >= 0 && qn > 1e-12f) ? 1.f / an : 0.f;
+        coef[B + i] = qp > 1e-12f ? sp / ap : 0.f;                       // clamp(min) passes no gradient below the floor
+        coef[2 * B + i] = (n >= 0 && qn > 1e-12f) ? sn / an : 0.f;
     }
 }
 
@@ -191,6 +206,67 @@ __global__ __launch_bounds__(256) void triplet_bwd_kernel(const float* __restric
         }
         df[(long)r * D + c] = k * acc;
     }
+}
+
+// normalize (layers/triplet_loss.py:5-13): y = x / (|x|_2 + 1e-12), one block per row (row stride ldx in, D out); norm[r] = |x_r|
+// is kept for the backward.  Not F.normalize's x / max(|x|, eps) (editor_l2norm_rows).
+__global__ __launch_bounds__(256) void normalize_rows_fwd_kernel(const float* __restrict__ x, long ldx, int D, float* __restrict__ y,
+    float* __restrict__ norm)
+{
+    __shared__ float red[16];
+    const float* xr = x + (long)blockIdx.x * ldx;
+    float s = 0.f;
+    for (int c = threadIdx.x; c < D; c += blockDim.x) s += xr[c] * xr[c];
+    s = block_sum(s, red);
+    const float n = sqrtf(s), den = n + 1e-12f;
+    if (threadIdx.x == 0) norm[blockIdx.x] = n;
+    for (int c = threadIdx.x; c < D; c += blockDim.x) y[(long)blockIdx.x * D + c] = xr[c] / den;
+}
+// what autograd gives for that expression: dx = g / (n + eps) - y (g . y) / n, the second term 0 at n = 0 (torch.norm's
+// subgradient there)
+__global__ __launch_bounds__(256) void normalize_rows_bwd_kernel(const float* __restrict__ g, const float* __restrict__ y,
+    const float* __restrict__ norm, int D, float* __restrict__ dx)
+{
+    __shared__ float red[16];
+    const float* gr = g + (long)blockIdx.x * D;
+    const float* yr = y + (long)blockIdx.x * D;
+    float s = 0.f;
+    for (int c = threadIdx.x; c < D; c += blockDim.x) s += gr[c] * yr[c];
+    s = block_sum(s, red);
+    const float n = norm[blockIdx.x], den = n + 1e-12f;
+    const float k = n == 0.f ? 0.f : s / n;
+    for (int c = threadIdx.x; c < D; c += blockDim.x)
+        dx[(long)blockIdx.x * D + c] = gr[c] / den - (n == 0.f ? 0.f : yr[c] * k);
+}
+
+// the forward of both triplet entries: squared norms, Gram matrix, mining, mean
+int triplet_forward(const float* feat, long ldf, const long* label, int B, int D, int form, float margin, float hard_factor,
+                    float* gram, float* sq, int* idx, float* coef, float* row_loss, float* dist, float* loss, int accumulate,
+                    editor_stream_t stream)
+{
+    if (B <= 1 || B > 1024 || D <= 0) return 1;                      // (B > 1024: the backward's LDS list, refused here already)
+    hipStream_t st = (hipStream_t)stream;
+    row_sqnorm_kernel<<<B, 256, 0, st>>>(feat, ldf, D, sq);
+    // gram = feat feat^T on the exact-fp32 matrix cores (B operand in the (N,K) nn.Linear layout = feat itself).  B x B
+    // is only (B/64)^2 output tiles: the reduction over D runs as a batch of 8 chunks into slabs behind `gram`, folded
+    // in a fixed order (100 -> ~15 us at B = 128, D = 2304; deterministic).
+    const int S = (D % 128 == 0 && D >= 1024) ? 8 : 1;
+    int rc;
+    if (S > 1) {
+        float* slabs = gram + (long)B * B;
+        const int kc = D / S;
+        rc = editor_gemm_f32(feat, feat, slabs, B, B, kc, ldf, ldf, B, 0, 0, S, kc, kc, (long)B * B, 1, 0, 0, 0, 1.f, 0.f, nullptr,
+                             nullptr, 1, EDITOR_EPI_NONE, nullptr, 0, stream);
+        if (!rc) rc = editor_reduce_rows(slabs, S, (long)B * B, gram, 0, 1.f, stream);
+    } else {
+        rc = editor_gemm_f32(feat, feat, gram, B, B, D, ldf, ldf, B, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1.f, 0.f, nullptr, nullptr, 1,
+                             EDITOR_EPI_NONE, nullptr, 0, stream);
+    }
+    if (rc) return rc;
+    triplet_mine_kernel<<<B, 256, 0, st>>>(gram, sq, label, B, form, margin, hard_factor, idx, coef, row_loss, dist);
+    sum_scalar_kernel<<<1, 256, 0, st>>>(row_loss, B, 1.f / (float)B, loss, accumulate);
+    EDITOR_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // namespace
@@ -291,27 +367,30 @@ int editor_ce_smooth_bwd(const float* logits, const long* target, int B, int C, 
 int editor_triplet_fwd(const float* feat, long ldf, const long* label, int B, int D, float* gram, float* sq, int* idx,
                        float* coef, float* row_loss, float* loss, int accumulate, editor_stream_t stream)
 {
-    if (B <= 1 || B > 1024 || D <= 0) return 1;                      // (B > 1024: the backward's LDS list, refused here already)
-    hipStream_t st = (hipStream_t)stream;
-    row_sqnorm_kernel<<<B, 256, 0, st>>>(feat, ldf, D, sq);
-    // gram = feat feat^T on the exact-fp32 matrix cores (B operand in the (N,K) nn.Linear layout = feat itself).  B x B
-    // is only (B/64)^2 output tiles: the reduction over D runs as a batch of 8 chunks into slabs behind `gram`, folded
-    // in a fixed order (100 -> ~15 us at B = 128, D = 2304; deterministic).
-    const int S = (D % 128 == 0 && D >= 1024) ? 8 : 1;
-    int rc;
-    if (S > 1) {
-        float* slabs = gram + (long)B * B;
-        const int kc = D / S;
-        rc = editor_gemm_f32(feat, feat, slabs, B, B, kc, ldf, ldf, B, 0, 0, S, kc, kc, (long)B * B, 1, 0, 0, 0, 1.f, 0.f, nullptr,
-                             nullptr, 1, EDITOR_EPI_NONE, nullptr, 0, stream);
-        if (!rc) rc = editor_reduce_rows(slabs, S, (long)B * B, gram, 0, 1.f, stream);
-    } else {
-        rc = editor_gemm_f32(feat, feat, gram, B, B, D, ldf, ldf, B, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1.f, 0.f, nullptr, nullptr, 1,
-                             EDITOR_EPI_NONE, nullptr, 0, stream);
-    }
-    if (rc) return rc;
-    triplet_mine_kernel<<<B, 256, 0, st>>>(gram, sq, label, B, idx, coef, row_loss);
-    sum_scalar_kernel<<<1, 256, 0, st>>>(row_loss, B, 1.f / (float)B, loss, accumulate);
+    return triplet_forward(feat, ldf, label, B, D, 0, 0.f, 0.f, gram, sq, idx, coef, row_loss, nullptr, loss, accumulate, stream);
+}
+
+int editor_triplet_loss_fwd(const float* feat, long ldf, const long* label, int B, int D, int form, float margin, float hard_factor,
+                            float* gram, float* sq, int* idx, float* coef, float* row_loss, float* dist, float* loss,
+                            int accumulate, editor_stream_t stream)
+{
+    if ((form != 0 && form != 1) || !dist) return 1;
+    return triplet_forward(feat, ldf, label, B, D, form, margin, hard_factor, gram, sq, idx, coef, row_loss, dist, loss, accumulate,
+                           stream);
+}
+
+int editor_normalize_rows_fwd(const float* x, long ldx, int B, int D, float* y, float* norm, editor_stream_t stream)
+{
+    if (B <= 0 || D <= 0 || ldx < D || !x || !y || !norm) return 1;
+    normalize_rows_fwd_kernel<<<B, 256, 0, (hipStream_t)stream>>>(x, ldx, D, y, norm);
+    EDITOR_LAUNCH_CHECK();
+    return 0;
+}
+
+int editor_normalize_rows_bwd(const float* g, const float* y, const float* norm, int B, int D, float* dx, editor_stream_t stream)
+{
+    if (B <= 0 || D <= 0 || !g || !y || !norm || !dx) return 1;
+    normalize_rows_bwd_kernel<<<B, 256, 0, (hipStream_t)stream>>>(g, y, norm, D, dx);
     EDITOR_LAUNCH_CHECK();
     return 0;
 }

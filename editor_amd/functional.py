@@ -1048,6 +1048,37 @@ class TripletSoftMarginFn(torch.autograd.Function):
         return ops.triplet_bwd(feat, idx, coef, dloss.contiguous().view(1).float()), None
 
 
+class TripletLossFn(torch.autograd.Function):
+    """TripletLoss(margin, hard_factor)(feat, labels, normalize_feature) (layers/triplet_loss.py:108-136): -> (loss, dist_ap, dist_an).
+    form 0 = SoftMarginLoss, 1 = MarginRankingLoss(margin).  The two distance vectors are outputs only (non-differentiable);
+    the backward is TripletSoftMarginFn's kernel for every form, followed by normalize's when the features were normalised."""
+
+    @staticmethod
+    def forward(ctx, feat, label, form, margin, hard_factor, normalize):
+        feat = feat.float()
+        if feat.stride(1) != 1:
+            feat = feat.contiguous()
+        norm = None
+        if normalize:
+            feat, norm = ops.normalize_rows_fwd(feat)
+        loss = torch.empty(1, dtype=torch.float32, device=feat.device)
+        idx, coef, dist = ops.triplet_loss_fwd(feat, label, form, margin, hard_factor, loss, accumulate=False)
+        b = feat.shape[0]
+        dist_ap, dist_an = dist[:b], dist[b:]
+        ctx.mark_non_differentiable(dist_ap, dist_an)
+        ctx.normalize = bool(normalize)
+        ctx.save_for_backward(feat, idx, coef, *(() if norm is None else (norm,)))
+        return loss.view(()), dist_ap, dist_an
+
+    @staticmethod
+    def backward(ctx, dloss, _dap, _dan):
+        feat, idx, coef = ctx.saved_tensors[:3]
+        df = ops.triplet_bwd(feat, idx, coef, dloss.contiguous().view(1).float())
+        if ctx.normalize:
+            df = ops.normalize_rows_bwd(df, feat, ctx.saved_tensors[3])
+        return df, None, None, None, None, None
+
+
 class GatherRowsFn(torch.autograd.Function):
     """out[r] = x2d[src[r]] (zeros where src[r] < 0): row movement between the dense token tensor and the packed
     layouts of the compacted HMA head.  Every source row is gathered at most once, so backward is a plain scatter."""

@@ -1076,18 +1076,51 @@ def ce_smooth_bwd(logits, target, eps, dloss):
     return d
 
 
+def _triplet_buffers(b, dev):
+    """gram (Gram matrix + 8 reduction-chunk slabs), sq, idx (2B) int32, coef (3B) fp32 of the triplet forward."""
+    return (torch.empty(9, b, b, dtype=torch.float32, device=dev), torch.empty(b, dtype=torch.float32, device=dev),
+            torch.empty(2 * b, dtype=torch.int32, device=dev), torch.empty(3 * b, dtype=torch.float32, device=dev))
+
+
 def triplet_fwd(feat, label, loss, accumulate):
     """Returns (idx (2B) int32, coef (3B) fp32) saved for backward."""
     feat, ldf = _rows_view(feat)
     b, d = feat.shape
     dev = feat.device
-    gram = torch.empty(9, b, b, dtype=torch.float32, device=dev)       # Gram matrix + 8 reduction-chunk slabs
-    sq = torch.empty(b, dtype=torch.float32, device=dev)
-    idx = torch.empty(2 * b, dtype=torch.int32, device=dev)
-    coef = torch.empty(3 * b, dtype=torch.float32, device=dev)
+    gram, sq, idx, coef = _triplet_buffers(b, dev)
     call("editor_triplet_fwd", _ptr(feat), ldf, label, b, d, gram, sq, idx, coef, workspace(dev, b), loss,
          1 if accumulate else 0)
     return idx, coef
+
+
+def triplet_loss_fwd(feat, label, form, margin, hard_factor, loss, accumulate):
+    """triplet_fwd with the reference's options (form 0 soft margin / 1 margin ranking, margin, hard_factor).
+    Returns (idx (2B) int32, coef (3B) fp32, dist (2B) fp32: scaled d_ap, d_an); idx / coef feed triplet_bwd unchanged."""
+    feat, ldf = _rows_view(feat)
+    b, d = feat.shape
+    dev = feat.device
+    gram, sq, idx, coef = _triplet_buffers(b, dev)
+    dist = torch.empty(2 * b, dtype=torch.float32, device=dev)
+    call("editor_triplet_loss_fwd", _ptr(feat), ldf, label, b, d, int(form), float(margin), float(hard_factor), gram, sq, idx, coef,
+         workspace(dev, b), dist, loss, 1 if accumulate else 0)
+    return idx, coef, dist
+
+
+def normalize_rows_fwd(x):
+    """layers/triplet_loss.py:5-13: -> y (B,D) = x / (||x|| + 1e-12), norm (B) (saved for the backward)."""
+    x, ldx = _rows_view(x)
+    b, d = x.shape
+    y = torch.empty(b, d, dtype=torch.float32, device=x.device)
+    norm = torch.empty(b, dtype=torch.float32, device=x.device)
+    call("editor_normalize_rows_fwd", _ptr(x), ldx, b, d, y, norm)
+    return y, norm
+
+
+def normalize_rows_bwd(g, y, norm):
+    b, d = y.shape
+    dx = torch.empty(b, d, dtype=torch.float32, device=y.device)
+    call("editor_normalize_rows_bwd", g, y, norm, b, d, dx)
+    return dx
 
 
 def triplet_bwd(feat, idx, coef, dloss):

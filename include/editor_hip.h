@@ -431,6 +431,20 @@ int editor_triplet_fwd(const float* feat, long ldf, const long* label, int B, in
                        float* coef, float* row_loss, float* loss, int accumulate, editor_stream_t stream);
 int editor_triplet_bwd(const float* feat, long ldf, int B, int D, const int* idx, const float* coef, const float* dloss,
                        float* dfeat, editor_stream_t stream);
+/* TripletLoss(margin, hard_factor) (layers/triplet_loss.py:108-136): editor_triplet_fwd with the reference's options.  With
+ * z = (1+hard_factor) d_ap - (1-hard_factor) d_an: form 0 = SoftMarginLoss, loss (+)= mean softplus(z) (margin unused);
+ * form 1 = MarginRankingLoss, loss (+)= mean max(z + margin, 0), whose derivative passes at z + margin == 0 as torch's clamp_min
+ * does.  dist (2B) receives the scaled distances the reference returns: dist[i] = (1+hard_factor) d_ap, dist[B+i] =
+ * (1-hard_factor) d_an.  The factors are folded into coef, so editor_triplet_bwd is the backward of every form.  A NaN distance
+ * gives a NaN loss and a NaN coef in both forms.  (form 0, hard_factor 0) computes editor_triplet_fwd's bits. */
+int editor_triplet_loss_fwd(const float* feat, long ldf, const long* label, int B, int D, int form, float margin, float hard_factor,
+                            float* gram, float* sq, int* idx, float* coef, float* row_loss, float* dist, float* loss,
+                            int accumulate, editor_stream_t stream);
+/* normalize (layers/triplet_loss.py:5-13): y (B,D) = x / (||x||_2 + 1e-12), x rows with stride ldx; norm (B) = ||x|| is saved for
+ * the backward dx (B,D) = g / (n + 1e-12) - y (g . y) / n (second term 0 at n = 0), g and y (B,D) contiguous.  Not
+ * editor_l2norm_rows, which is F.normalize's x / max(||x||, eps). */
+int editor_normalize_rows_fwd(const float* x, long ldx, int B, int D, float* y, float* norm, editor_stream_t stream);
+int editor_normalize_rows_bwd(const float* g, const float* y, const float* norm, int B, int D, float* dx, editor_stream_t stream);
 
 /* ---- retrieval evaluation (utils/metrics.py consumes the hot path's eval-mode features) ------ */
 

@@ -79,15 +79,24 @@ def install_weight_copies(pairs, transposed=False):
 DGRAD_KMAJOR = os.environ.get("EDITOR_DGRAD_KMAJOR", "1") != "0"
 
 
-def act_weight_t(w, dtype):
-    """16-bit W^T (contiguous) of a 2-D fp32 master weight, cached like act_weight (FusedSGD refreshes it in its own launch)."""
-    key = (id(w), dtype, "T")
+def _cached(key, w, make):
+    """The operand cache's one lookup.  Entries are cached per parameter OBJECT and made again (`make()`) when the parameter's version
+    counter moves (optimizer step, load_state_dict), its storage moves or the epoch does.  An entry holds a weak reference so that a
+    recycled id()/address of a freed parameter can never serve stale weights."""
     ent = _BF16_CACHE.get(key)
     ver = w._version
     if ent is None or ent[0]() is not w or ent[1] != ver or ent[3] != w.data_ptr() or ent[4] != _WEIGHT_EPOCH:
-        ent = (weakref.ref(w), ver, act_weight(w, dtype).t().contiguous(), w.data_ptr(), _WEIGHT_EPOCH)
+        if len(_BF16_CACHE) > 4096:                       # drop entries of dead parameters
+            for k in [k for k, e in _BF16_CACHE.items() if e[0]() is None]:
+                del _BF16_CACHE[k]
+        ent = (weakref.ref(w), ver, make(), w.data_ptr(), _WEIGHT_EPOCH)
         _BF16_CACHE[key] = ent
     return ent[2]
+
+
+def act_weight_t(w, dtype):
+    """16-bit W^T (contiguous) of a 2-D fp32 master weight, cached like act_weight (FusedSGD refreshes it in its own launch)."""
+    return _cached((id(w), dtype, "T"), w, lambda: act_weight(w, dtype).t().contiguous())
 
 
 # Activation-light blocks (cfg.MODEL.ACT_LIGHT; BASELINE config 5 at B = 64 per GPU does not fit otherwise): a block saves
@@ -106,13 +115,7 @@ F16X2H = "f16x2h"    # ... of a block whose attention MAP must be fp32-class but
 def act_weight_split(w):
     """fp32 master weight -> the (hi, lo) half pair of w * ops.SPLIT_WSCALE (forward operand of the 'f16x2' mode), cached like
     act_weight (FusedSGD refreshes the pairs in its own launch)."""
-    key = (id(w), F16X2)
-    ent = _BF16_CACHE.get(key)
-    ver = w._version
-    if ent is None or ent[0]() is not w or ent[1] != ver or ent[3] != w.data_ptr() or ent[4] != _WEIGHT_EPOCH:
-        ent = (weakref.ref(w), ver, ops.split_f32(w.detach(), ops.SPLIT_WSCALE), w.data_ptr(), _WEIGHT_EPOCH)
-        _BF16_CACHE[key] = ent
-    return ent[2]
+    return _cached((id(w), F16X2), w, lambda: ops.split_f32(w.detach(), ops.SPLIT_WSCALE))
 
 
 def install_weight_pairs(triples):
@@ -122,22 +125,10 @@ def install_weight_pairs(triples):
 
 
 def act_weight(w, dtype):
-    """fp32 master parameter -> GEMM operand dtype.  16-bit copies are cached per parameter OBJECT and re-cast when
-    the parameter's version counter moves (optimizer step, load_state_dict).  The entry holds a weak reference so
-    that a recycled id()/address of a freed parameter can never serve stale weights."""
+    """fp32 master parameter -> GEMM operand dtype (16-bit copies come from the operand cache, see _cached)."""
     if dtype == torch.float32:
         return w.detach()
-    key = (id(w), dtype)
-    ent = _BF16_CACHE.get(key)
-    ver = w._version
-    if ent is None or ent[0]() is not w or ent[1] != ver or ent[3] != w.data_ptr() or ent[4] != _WEIGHT_EPOCH:
-        if len(_BF16_CACHE) > 4096:                       # drop entries of dead parameters
-            for k in [k for k, e in _BF16_CACHE.items() if e[0]() is None]:
-                del _BF16_CACHE[k]
-        ent = (weakref.ref(w), ver, ops.cast(w.detach().contiguous().view(-1), dtype).view(w.shape),
-               w.data_ptr(), _WEIGHT_EPOCH)
-        _BF16_CACHE[key] = ent
-    return ent[2]
+    return _cached((id(w), dtype), w, lambda: ops.cast(w.detach().contiguous().view(-1), dtype).view(w.shape))
 
 
 def _linear_fwd(x2d, w_act, bias, out_dtype, m_live=None):
@@ -188,8 +179,6 @@ def join_side_stream(device):
 #     NaN losses) - so the launch is joined before the block's backward returns.
 GROUP_WGRAD = os.environ.get("EDITOR_GROUP_WGRAD", "1") != "0"
 WGRAD_DEFER_JOIN = os.environ.get("EDITOR_WGRAD_DEFER", "1") != "0"       # measurement switch: 0 = join at the end of each block
-
-
 DEFER_REDUCE = os.environ.get("EDITOR_DEFER_REDUCE", "1") != "0"     # measurement switch: ops.ReduceQueue in the block backward
 
 
@@ -208,17 +197,17 @@ class _GemmReq:
 
 
 class _WgradReq:
-    __slots__ = ("jobs", "m", "alpha", "m_live", "deferred", "dev")
+    __slots__ = ("jobs", "m", "alpha", "m_live", "deferred", "dev", "side")
 
-    def __init__(self, jobs, m, alpha, m_live, deferred, dev):
-        self.jobs, self.m, self.alpha, self.m_live, self.deferred, self.dev = jobs, m, alpha, m_live, deferred, dev
+    def __init__(self, jobs, m, alpha, m_live, deferred, dev, side):
+        self.jobs, self.m, self.alpha, self.m_live, self.deferred, self.dev, self.side = jobs, m, alpha, m_live, deferred, dev, side
 
 
 def _run_wgrads(reqs):
     """the grouped weight-gradient launches of one or several blocks: side stream (joined one block later when the gradients land in
-    sinks, see GROUP_WGRAD below) or inline"""
+    sinks, see GROUP_WGRAD below) or inline - as the blocks' forwards decided (_BlockOpts.side_stream; lockstep blocks agree)"""
     dev = reqs[0].dev
-    if WGRAD_SIDE_STREAM:
+    if reqs[0].side:
         if any(r.deferred for r in reqs):
             join_side_stream(dev)                   # the PREVIOUS block's grouped launch (had a whole block of slack)
         ready = torch.cuda.current_stream(dev).record_event()
@@ -338,18 +327,17 @@ class _CastBox:
         return h[1], h[2]
 
 
-def _cast_boxes(ctx, x, out, m, d, act_dtype, mask, cu, m_live, rowscale_mlp, has_fc2_bias, sink, plain, perm=None):
-    """forward side of HANDOFF_CAST: ctx.feeds_box = the box of the block whose output `x` is; ctx.box = this block's own."""
-    prev, _CAST_SLOT[0] = _CAST_SLOT[0], None
-    ctx.feeds_box = ctx.box = None
-    if not (HANDOFF_CAST and FUSE_LN_CAST and plain and act_dtype in ops.HALF_DTYPES and cu is None and mask is None
-            and m_live is None and d % 256 == 0 and d <= 1024):
-        return
-    if prev is not None and prev.out() is x and prev.m == m and prev.dtype == act_dtype:
-        ctx.feeds_box = prev
-    ctx.box = _CAST_SLOT[0] = _CastBox(out, m, act_dtype, rowscale_mlp, has_fc2_bias, grad_scale(act_dtype),
-                                       sink.views[11] if sink is not None else None, perm)
+# ---- the shape predicates of the block's launch decisions, each written once (_decide_block, _linear_bwd_gen, _scaled_cast_colsum)
+def _big_launch(m):                      # enough token rows for the k-major dgrads and the side-stream weight gradients to pay
+    return m >= 2048
 
+
+def _row_kernel_width(d):                # widths the fused row kernels take (ops.layernorm_bwd_cast, ops.cast_rows_colsum)
+    return d % 256 == 0 and d <= 1024
+
+
+def _group_wgrad_shape(m, d, hidden):    # four weight gradients in 256 x 256 tiles over whole 64-row K-tiles (ops.gemm_wgrad_group)
+    return _big_launch(m) and m % 64 == 0 and d % 256 == 0 and hidden % 256 == 0
 
 
 def _linear_bwd(*args, **kw):
@@ -358,17 +346,18 @@ def _linear_bwd(*args, **kw):
 
 
 def _linear_bwd_gen(dy, x2d, w_act, need_bias, gelu_pre=None, m_live=None, db=None, dx_colsum=None, gs=1.0, dw_out=None,
-                    db_out=None, dxcs_out=None, w_t=None, defer=None, aux_is_grad=True, rq=None, live_dense=False):
+                    db_out=None, dxcs_out=None, w_t=None, defer=None, aux_is_grad=True, rq=None, live_dense=False, side=None):
     """dx = dy W (optionally * gelu'(gelu_pre), fused epilogue) ; dW = dy^T x (fp32) ; db = colsum(dy) (or the
     caller's, when the kernel that produced dy summed its columns on the way).  dx_colsum: also return colsum(dx) - the
     bias gradient of the layer BELOW - from the dgrad's own epilogue when it can deliver it (else None).
     gs: loss scale carried by dy (f16 mode): dx keeps it, dW / db / the returned column sums have it divided out.
     dw_out / db_out / dxcs_out: write the weight gradient / bias gradient / column sums of dx THERE (views of a gradient
-    bucket, editor_amd.ddp.GradBuckets) instead of into fresh tensors."""
+    bucket, editor_amd.ddp.GradBuckets) instead of into fresh tensors.
+    side: the weight gradient on the side stream - a block's forward-time decision; None = WGRAD_SIDE_STREAM as it stands now."""
     m, n = dy.shape
     k = x2d.shape[1]
     inv = 1.0 / gs
-    use_side = WGRAD_SIDE_STREAM and dy.dtype in ops.HALF_DTYPES and m >= 2048
+    use_side = (WGRAD_SIDE_STREAM if side is None else side) and dy.dtype in ops.HALF_DTYPES and _big_launch(m)
     dy_ready = torch.cuda.current_stream(dy.device).record_event() if use_side else None   # BEFORE the dgrad launch
     dx = torch.empty(m, k, dtype=x2d.dtype, device=dy.device)
     dxcs = None
@@ -386,11 +375,9 @@ def _linear_bwd_gen(dy, x2d, w_act, need_bias, gelu_pre=None, m_live=None, db=No
                        aux=gelu_pre, m_live=m_live,
                        colsum=dxcs, colsum_scale=inv, tag="dgrad", rq=rq, live_dense=live_dense)
     dw = dw_out if dw_out is not None else torch.empty(n, k, dtype=torch.float32, device=dy.device)
-    if need_bias and db is None:
+    need_colsum = bool(need_bias) and db is None
+    if need_colsum:
         db = db_out if db_out is not None else torch.empty(n, dtype=torch.float32, device=dy.device)
-        need_colsum = True
-    else:
-        need_colsum = False
     if need_colsum and m_live is not None:
         #  ops.colsum sums ALL m rows; behind *m_live the rows of dy are unwritten (cast_rows / the dgrads skip dead tiles).
         # The only live-row products are the compacted HMA head's, whose linears have no bias (vit_pytorch.py:232-237,150-156).
@@ -447,12 +434,39 @@ def _splitk_for(n_out, k_out, m_red, cus=256):
 DROP_SKIP = os.environ.get("EDITOR_DROP_SKIP", "1") != "0"      # A/B switch: stochastic-depth compaction of the MLP branch
 
 
-def _plan_ok(act_dtype, m, d, hidden, cu, mask, m_live, branch16, defer_out, pend_branch, rowscale_mlp):
-    """Can this block run its MLP branch on the stochastic-depth-compacted rows?  The plain dense 16-bit block whose backward takes
-    the grouped weight gradients, the deferred reductions and the fused LayerNorm casts (every condition backward_gen re-derives)."""
-    return (DROP_SKIP and rowscale_mlp is not None and act_dtype in ops.HALF_DTYPES and cu is None and mask is None and m_live is None
-            and not branch16 and not defer_out and pend_branch is None and not ACT_LIGHT and GROUP_WGRAD and DEFER_REDUCE
-            and FUSE_LN_CAST and m >= 2048 and m % 64 == 0 and d % 256 == 0 and d <= 1024 and hidden % 256 == 0)
+class _BlockOpts:
+    """What one transformer block's forward decided (_decide_block) - its backward branches on this record and on nothing else, so a
+    switch that moves between the two (a second model, set_model_options, a test's `finally`) cannot split a block's two halves."""
+    __slots__ = ("half", "light", "plan_ok", "group_wgrad", "defer_reduce", "fuse_cast", "handoff", "kmajor", "side_stream",
+                 "defer_join", "wgrad_ln", "save_aux", "gs")
+
+
+def _decide_block(act_dtype, m, d, hidden, has_cu=False, has_mask=False, has_m_live=False, has_sink=False, has_rowscale_mlp=False,
+                  has_pend=False, branch16=False, defer_out=False, can_backward=True):
+    """Every launch decision of a block's forward and backward from plain values and the module switches as they stand NOW (no
+    tensors, no GPU).  act_dtype: a torch dtype or the F16X2 / F16X2H marker; can_backward: some input requires a gradient."""
+    o = _BlockOpts()
+    dtype = torch.float16 if act_dtype in (F16X2, F16X2H) else act_dtype      # (split-precision forward: an f16 backward either way)
+    half = o.half = dtype in ops.HALF_DTYPES
+    o.gs = grad_scale(dtype)                         # (the model's loss scale at forward time: the backward uses THIS one)
+    o.light = bool(ACT_LIGHT and half and act_dtype != F16X2)     # (the all-split forward saves its hi halves as they are)
+    # a no-grad forward - model.eval() under torch.no_grad(), engine/processor.py:217-270 - saves nothing for a backward: the
+    # 16-bit fc1 epilogue then writes ONE output instead of two, 304 MB per layer less at B = 128
+    o.save_aux = bool(FWD_GRAD and can_backward) or not half
+    o.group_wgrad = GROUP_WGRAD and half and _group_wgrad_shape(m, d, hidden)
+    o.defer_reduce = DEFER_REDUCE and o.group_wgrad               # (only there: every producer then runs on one stream)
+    o.fuse_cast = FUSE_LN_CAST and half and not has_mask and not has_m_live and _row_kernel_width(d)
+    # LayerNorm-1's fused pass also serves the block BELOW (see HANDOFF_CAST): plain dense blocks that return x2
+    o.handoff = HANDOFF_CAST and o.fuse_cast and not has_cu and not has_pend and not branch16 and not defer_out
+    o.kmajor = DGRAD_KMAJOR and half and _big_launch(m)
+    o.side_stream = WGRAD_SIDE_STREAM and half and _big_launch(m)
+    o.defer_join = o.group_wgrad and has_sink and WGRAD_SIDE_STREAM and WGRAD_DEFER_JOIN
+    o.wgrad_ln = WGRAD_LN and o.group_wgrad and o.fuse_cast and not o.defer_join
+    # Can the MLP branch run on the stochastic-depth-compacted rows?  The plain dense 16-bit block whose backward takes the grouped
+    # weight gradients, the deferred reductions and the fused LayerNorm casts.
+    o.plan_ok = (DROP_SKIP and has_rowscale_mlp and not has_cu and not branch16 and not defer_out and not has_pend and not ACT_LIGHT
+                 and o.group_wgrad and o.defer_reduce and o.fuse_cast)       # (fuse_cast: no row mask, no live-row count)
+    return o
 
 
 class TransformerBlockFn(torch.autograd.Function):
@@ -503,19 +517,20 @@ class TransformerBlockFn(torch.autograd.Function):
         # computed: LayerNorm-2 writes the live samples' rows compacted, fc1 / fc2 and the whole MLP backward run on that prefix
         # (`live` rows, a device scalar: tiles beyond it exit), the fc2 epilogue scatters back.  Same bits for every live row.
         # (the split-precision modes: the MLP's forward on half pairs - or, F16X2H, as plain f16 - and an f16 backward either way)
-        plan_ok = _plan_ok(torch.float16 if act_dtype in (F16X2, F16X2H) else act_dtype, m, d, fc1w.shape[0], cu, mask,
-                           m_live, branch16, defer_out, pend_branch, rowscale_mlp)
-        plan = drop_plan if plan_ok else None
-        ctx.plan = plan
-        head_done = split_all = False
-        if act_dtype in (F16X2, F16X2H):
+        hidden = fc1w.shape[0]
+        o = ctx.opts = _decide_block(act_dtype, m, d, hidden, cu is not None, mask is not None, m_live is not None, sink is not None,
+                                     rowscale_mlp is not None, pend_branch is not None, branch16, defer_out,
+                                     any(ctx.needs_input_grad))
+        plan = ctx.plan = drop_plan if o.plan_ok else None
+        live = plan[2] if plan is not None else m_live
+        br2 = None
+        head_done, split_all = act_dtype == F16X2H, act_dtype == F16X2
+        if head_done or split_all:
             # split-precision forward: every product on half PAIRS (three MFMA passes, fp32-class), the exact softmax / GELU
             # on unrounded values; what is saved for the (16-bit) backward are the hi halves - plain f16 tensors
-            head_only = act_dtype == F16X2H
             act_dtype = torch.float16
             inv_ws = 1.0 / ops.SPLIT_WSCALE
             wq = act_weight_split(qkvw)
-            hidden = fc1w.shape[0]
             h1, h1l, mean1, rstd1 = ops.layernorm_fwd_split(x2d, n1w, n1b, eps, mask, m_live)
             qkv = torch.empty(m, 3 * d, dtype=act_dtype, device=x.device)
             qkvl = torch.empty_like(qkv)
@@ -527,7 +542,6 @@ class TransformerBlockFn(torch.autograd.Function):
             if isinstance(probs_out, list):            # no probability tensor: the rollout recomputes it from the q / k pairs
                 probs_out.append((qkv, qkvl, attn_saved))
             del qkvl
-            head_done, split_all = head_only, not head_only
         if head_done:
             del aol                          # F16X2H: the projection and the MLP below, on the hi halves, as the f16 mode
         if split_all:
@@ -541,8 +555,7 @@ class TransformerBlockFn(torch.autograd.Function):
                 h2, h2l, mean2, rstd2 = ops.layernorm_fwd_split_perm(x1, n2w, n2b, eps, plan[0], rowscale_mlp, x2)
             else:
                 h2, h2l, mean2, rstd2 = ops.layernorm_fwd_split(x1, n2w, n2b, eps, mask, m_live)
-            live = plan[2] if plan is not None else m_live
-            a = torch.empty(m, hidden, dtype=act_dtype, device=x.device) if (FWD_GRAD and any(ctx.needs_input_grad)) else None
+            a = torch.empty(m, hidden, dtype=act_dtype, device=x.device) if o.save_aux else None
             g = torch.empty(m, hidden, dtype=act_dtype, device=x.device)
             gl = torch.empty_like(g)
             ops.gemm_split((h2, h2l), w1, g, gl, m, hidden, d, alpha=inv_ws, bias=fc1b, epilogue=ops.EPI_GELU | ops.EPI_AUX_GRAD,
@@ -552,88 +565,75 @@ class TransformerBlockFn(torch.autograd.Function):
                            epilogue=ops.EPI_RESIDUAL, aux=x1, m_live=live, live_dense=plan is not None,
                            rowmap=plan[1] if plan is not None else None)
             del gl
-            ctx.save_for_backward(x2d, mean1, rstd1, h1, qkv, ao, x1, mean2, rstd2, h2, a, g, n1w, n2w,
-                                  qkvw, projw, fc1w, fc2w, mask, attn_saved, rowscale_attn, rowscale_mlp, cu, m_live)
-            ctx.light = None
-            ctx.gs = grad_scale(act_dtype)
-            ctx.meta = (b, t, d, heads, act_dtype, qkvb is not None, projb is not None, fc1b is not None, fc2b is not None,
-                        tuple(x.shape), qk_scale, sink)
-            out = x2.view(x.shape)
-            _cast_boxes(ctx, x, out, m, d, act_dtype, mask, cu, m_live, rowscale_mlp, fc2b is not None, sink, True,
-                        plan[0] if plan is not None else None)
-            return out
-        wp, w1, w2 = (act_weight(w, act_dtype) for w in (projw, fc1w, fc2w))
-        if not head_done:
-            wq = act_weight(qkvw, act_dtype)
-            if pend_branch is not None:          # x2d <- x1_prev + rs_prev * fc2-branch_prev, h1 = LN1(x2d): one pass
-                x2d, h1, mean1, rstd1 = ops.resid_add_layernorm_fwd(x2d, pend_branch, pend_rs, n1w, n1b, eps)
-            else:
-                h1, mean1, rstd1 = ops.layernorm_fwd(x2d, n1w, n1b, eps, act_dtype, mask, 0, m_live=m_live)
-            qkv = torch.empty(m, 3 * d, dtype=act_dtype, device=x.device)
-            yield _GemmReq(h1, wq, qkv, m, 3 * d, d, d, d, 3 * d, 0, 0, bias=qkvb, m_live=m_live,
-                           epilogue=STAGGER_QKV if m_live is None else 0)
-            if isinstance(probs_out, list):            # bf16 backbone: no probability tensor; the rollout recomputes it
-                ao, attn_saved = ops.attention_fwd(qkv, b, t, heads, hd, amask, None, cu=cu, scale=qk_scale)
-                probs_out.append((qkv, attn_saved))
-            else:
-                ao, attn_saved = ops.attention_fwd(qkv, b, t, heads, hd, amask, probs_out, cu=cu, scale=qk_scale)
-        if branch16:                                # 16-bit branch, plain epilogue; x1 = x + rs * branch inside LayerNorm-2's pass
-            br1 = torch.empty(m, d, dtype=act_dtype, device=x.device)
-            ops.gemm(ao, wp, br1, m, d, d, d, d, d, 0, 0, bias=projb)
-            x1, h2, mean2, rstd2 = ops.resid_add_layernorm_fwd(x2d, br1, rowscale_attn, n2w, n2b, eps)
-            del br1
         else:
-            x1 = torch.empty_like(x2d)              # x1 = x + rs * (ao Wp^T + b): residual add in the GEMM epilogue
-            yield _GemmReq(ao, wp, x1, m, d, d, d, d, d, 0, 0, bias=projb, rowscale=rowscale_attn,
-                           epilogue=ops.EPI_RESIDUAL | (STAGGER_PROJ if m_live is None else 0), aux=x2d, m_live=m_live)
-            if plan is not None:
-                x2 = torch.empty_like(x2d)          # (dropped rows: LayerNorm-2 copies x1 there; live rows: the fc2 epilogue)
-                h2, mean2, rstd2 = ops.layernorm_fwd_perm(x1, n2w, n2b, eps, act_dtype, plan[0], rowscale_mlp, x2)
+            wp, w1, w2 = (act_weight(w, act_dtype) for w in (projw, fc1w, fc2w))
+            if not head_done:
+                wq = act_weight(qkvw, act_dtype)
+                if pend_branch is not None:          # x2d <- x1_prev + rs_prev * fc2-branch_prev, h1 = LN1(x2d): one pass
+                    x2d, h1, mean1, rstd1 = ops.resid_add_layernorm_fwd(x2d, pend_branch, pend_rs, n1w, n1b, eps)
+                else:
+                    h1, mean1, rstd1 = ops.layernorm_fwd(x2d, n1w, n1b, eps, act_dtype, mask, 0, m_live=m_live)
+                qkv = torch.empty(m, 3 * d, dtype=act_dtype, device=x.device)
+                yield _GemmReq(h1, wq, qkv, m, 3 * d, d, d, d, 3 * d, 0, 0, bias=qkvb, m_live=m_live,
+                               epilogue=STAGGER_QKV if m_live is None else 0)
+                if isinstance(probs_out, list):            # bf16 backbone: no probability tensor; the rollout recomputes it
+                    ao, attn_saved = ops.attention_fwd(qkv, b, t, heads, hd, amask, None, cu=cu, scale=qk_scale)
+                    probs_out.append((qkv, attn_saved))
+                else:
+                    ao, attn_saved = ops.attention_fwd(qkv, b, t, heads, hd, amask, probs_out, cu=cu, scale=qk_scale)
+            if branch16:                                # 16-bit branch, plain epilogue; x1 = x + rs * branch inside LayerNorm-2's pass
+                br1 = torch.empty(m, d, dtype=act_dtype, device=x.device)
+                ops.gemm(ao, wp, br1, m, d, d, d, d, d, 0, 0, bias=projb)
+                x1, h2, mean2, rstd2 = ops.resid_add_layernorm_fwd(x2d, br1, rowscale_attn, n2w, n2b, eps)
+                del br1
             else:
-                h2, mean2, rstd2 = ops.layernorm_fwd(x1, n2w, n2b, eps, act_dtype, mask, 0, m_live=m_live)
-        hidden = w1.shape[0]
-        # (a no-grad forward - model.eval() under torch.no_grad(), engine/processor.py:217-270 - saves nothing for a backward: the
-        #  16-bit fc1 epilogue then writes ONE output instead of two, 304 MB per layer less at B = 128)
-        need_a = (FWD_GRAD and any(ctx.needs_input_grad)) or act_dtype not in ops.HALF_DTYPES
-        a = torch.empty(m, hidden, dtype=act_dtype, device=x.device) if need_a else None
-        g = torch.empty(m, hidden, dtype=act_dtype, device=x.device)
-        # 16-bit modes: `a` receives gelu'(pre-activation) - all the backward needs of it (one multiply in the fc2 dgrad
-        # epilogue instead of an erfc + exponential per element); the f32 parity kernels keep the pre-activation
-        light = ACT_LIGHT and act_dtype in ops.HALF_DTYPES
-        ag = ops.EPI_AUX_GRAD if (act_dtype in ops.HALF_DTYPES and not light) else 0     # light: `a` keeps the pre-activation
-        live = plan[2] if plan is not None else m_live
-        yield _GemmReq(h2, w1, g, m, hidden, d, d, d, hidden, 0, 0, bias=fc1b, epilogue=ops.EPI_GELU | ag, aux=a, m_live=live,
-                       live_dense=plan is not None)
-        br2 = None
-        if defer_out:                               # (x1, fc2 branch): the consumer's LayerNorm adds them
-            br2 = torch.empty(m, d, dtype=act_dtype, device=x.device)
-            ops.gemm(g, w2, br2, m, d, hidden, hidden, hidden, d, 0, 0, bias=fc2b)
-        elif plan is not None:
-            yield _GemmReq(g, w2, x2, m, d, hidden, hidden, hidden, d, 0, 0, bias=fc2b, rowscale=rowscale_mlp,
-                           epilogue=ops.EPI_RESIDUAL, aux=x1, m_live=live, live_dense=True, rowmap=plan[1])
-        else:
-            x2 = torch.empty_like(x2d)
-            # plan_ok without a plan (cfg.MODEL.DROP_SKIP off): the product takes the ping-pong kernel, as its compacted form must (the
-            # row scatter is that kernel's epilogue) - at few token rows (two modalities at B = 32: 8 256) the tile-count heuristic of
-            # ops.gemm would pick the 256x128 kernel, whose fp32 sums round differently, and the switch would change the forward's bits
-            yield _GemmReq(g, w2, x2, m, d, hidden, hidden, hidden, d, 0, 0, bias=fc2b, rowscale=rowscale_mlp,
-                           epilogue=ops.EPI_RESIDUAL | (ops.EPI_FORCE_PP if plan_ok else 0), aux=x1, m_live=m_live)
-        if light:
+                x1 = torch.empty_like(x2d)              # x1 = x + rs * (ao Wp^T + b): residual add in the GEMM epilogue
+                yield _GemmReq(ao, wp, x1, m, d, d, d, d, d, 0, 0, bias=projb, rowscale=rowscale_attn,
+                               epilogue=ops.EPI_RESIDUAL | (STAGGER_PROJ if m_live is None else 0), aux=x2d, m_live=m_live)
+                if plan is not None:
+                    x2 = torch.empty_like(x2d)          # (dropped rows: LayerNorm-2 copies x1 there; live rows: the fc2 epilogue)
+                    h2, mean2, rstd2 = ops.layernorm_fwd_perm(x1, n2w, n2b, eps, act_dtype, plan[0], rowscale_mlp, x2)
+                else:
+                    h2, mean2, rstd2 = ops.layernorm_fwd(x1, n2w, n2b, eps, act_dtype, mask, 0, m_live=m_live)
+            a = torch.empty(m, hidden, dtype=act_dtype, device=x.device) if o.save_aux else None
+            g = torch.empty(m, hidden, dtype=act_dtype, device=x.device)
+            # 16-bit modes: `a` receives gelu'(pre-activation) - all the backward needs of it (one multiply in the fc2 dgrad
+            # epilogue instead of an erfc + exponential per element); the f32 parity kernels keep the pre-activation
+            ag = ops.EPI_AUX_GRAD if (act_dtype in ops.HALF_DTYPES and not o.light) else 0     # light: `a` keeps the pre-activation
+            yield _GemmReq(h2, w1, g, m, hidden, d, d, d, hidden, 0, 0, bias=fc1b, epilogue=ops.EPI_GELU | ag, aux=a, m_live=live,
+                           live_dense=plan is not None)
+            if defer_out:                               # (x1, fc2 branch): the consumer's LayerNorm adds them
+                br2 = torch.empty(m, d, dtype=act_dtype, device=x.device)
+                ops.gemm(g, w2, br2, m, d, hidden, hidden, hidden, d, 0, 0, bias=fc2b)
+            elif plan is not None:
+                yield _GemmReq(g, w2, x2, m, d, hidden, hidden, hidden, d, 0, 0, bias=fc2b, rowscale=rowscale_mlp,
+                               epilogue=ops.EPI_RESIDUAL, aux=x1, m_live=live, live_dense=True, rowmap=plan[1])
+            else:
+                x2 = torch.empty_like(x2d)
+                # plan_ok without a plan (cfg.MODEL.DROP_SKIP off): the product takes the ping-pong kernel, as its compacted form must (the
+                # row scatter is that kernel's epilogue) - at few token rows (two modalities at B = 32: 8 256) the tile-count heuristic of
+                # ops.gemm would pick the 256x128 kernel, whose fp32 sums round differently, and the switch would change the forward's bits
+                yield _GemmReq(g, w2, x2, m, d, hidden, hidden, hidden, d, 0, 0, bias=fc2b, rowscale=rowscale_mlp,
+                               epilogue=ops.EPI_RESIDUAL | (ops.EPI_FORCE_PP if o.plan_ok else 0), aux=x1, m_live=m_live)
+        if o.light:
             h1 = h2 = g = None                      # recomputed by the backward (n1b / n2b / eps ride along)
         ctx.save_for_backward(x2d, mean1, rstd1, h1, qkv, ao, x1, mean2, rstd2, h2, a, g, n1w, n2w,
                               qkvw, projw, fc1w, fc2w, mask, attn_saved, rowscale_attn, rowscale_mlp, cu, m_live)
-        ctx.light = (n1b, n2b, float(eps)) if light else None
-        ctx.gs = grad_scale(act_dtype)               # (the model's loss scale at forward time: the backward uses THIS one)
+        ctx.light = (n1b, n2b, float(eps)) if o.light else None
         ctx.meta = (b, t, d, heads, act_dtype, qkvb is not None, projb is not None, fc1b is not None, fc2b is not None,
                     tuple(x.shape), qk_scale, sink)
+        # forward side of HANDOFF_CAST: ctx.feeds_box = the box of the block whose output `x` is; ctx.box = this block's own
+        prev, _CAST_SLOT[0] = _CAST_SLOT[0], None
+        ctx.feeds_box = ctx.box = None
         if defer_out:
             ctx.mark_non_differentiable(br2)
-            _CAST_SLOT[0] = None
-            ctx.feeds_box = ctx.box = None
             return x1.view(x.shape), br2
         out = x2.view(x.shape)
-        _cast_boxes(ctx, x, out, m, d, act_dtype, mask, cu, m_live, rowscale_mlp, fc2b is not None, sink,
-                    pend_branch is None and not branch16, plan[0] if plan is not None else None)
+        if o.handoff:
+            if prev is not None and prev.out() is x and prev.m == m and prev.dtype == act_dtype:
+                ctx.feeds_box = prev
+            ctx.box = _CAST_SLOT[0] = _CastBox(out, m, act_dtype, rowscale_mlp, fc2b is not None, o.gs,
+                                               sink.views[11] if sink is not None else None, plan[0] if plan is not None else None)
         return out
 
     @staticmethod
@@ -643,17 +643,17 @@ class TransformerBlockFn(torch.autograd.Function):
         b, t, d, heads, act_dtype, hb_qkv, hb_proj, hb_fc1, hb_fc2, xshape, qk_scale, sink = ctx.meta
         # gradient outputs in forward-argument order: n1w n1b qkvw qkvb projw projb n2w n2b fc1w fc1b fc2w fc2b
         sv = sink.views if sink is not None else [None] * 12
-        gs = ctx.gs                                  # f16: half gradients travel loss-scaled (1.0 otherwise)
+        o = ctx.opts                                 # what the forward decided (_decide_block): no module switch is read below
+        gs = o.gs                                    # f16: half gradients travel loss-scaled (1.0 otherwise)
         m = x2d.shape[0]
         hd = d // heads
         amask = None if cu is not None else mask
         wq, wp, w1, w2 = (act_weight(w, act_dtype) for w in (qkvw, projw, fc1w, fc2w))
-        kmaj = DGRAD_KMAJOR and act_dtype in ops.HALF_DTYPES and m >= 2048
-        wqt, wpt, w1t, w2t = ((act_weight_t(w, act_dtype) for w in (qkvw, projw, fc1w, fc2w)) if kmaj else (None,) * 4)
+        wqt, wpt, w1t, w2t = ((act_weight_t(w, act_dtype) for w in (qkvw, projw, fc1w, fc2w)) if o.kmajor else (None,) * 4)
         dx2 = dx2.contiguous().view(m, d)
         light = ctx.light
         if a is None:
-            # the forward ran with the grad mode off (FWD_GRAD False: fc1 then writes no gelu' tensor) - a backward through it would
+            # the forward ran with the grad mode off (_BlockOpts.save_aux False: fc1 then writes no gelu' tensor) - a backward through it would
             # silently drop gelu' from the fc2 dgrad; it cannot happen through EDITOR.forward, which restores the flag
             raise RuntimeError("TransformerBlockFn.backward: this block's forward saved no GELU derivative (it ran under "
                                "functional.set_model_options(grad_enabled=False)); re-run the forward with gradients enabled")
@@ -661,22 +661,16 @@ class TransformerBlockFn(torch.autograd.Function):
             # activation-light block: the GELU output for the fc2 weight gradient from the saved pre-activation (the fc2 dgrad
             # epilogue evaluates gelu' from it as well); the LayerNorm outputs right before their weight gradients need them
             g = ops.gelu_fwd(a)
-        hidden = fc1w.shape[0]
-        jobs = [] if (GROUP_WGRAD and act_dtype in ops.HALF_DTYPES and m >= 2048 and m % 64 == 0 and d % 256 == 0
-                      and hidden % 256 == 0) else None
-        deferred = jobs is not None and sink is not None and WGRAD_SIDE_STREAM and WGRAD_DEFER_JOIN
+        jobs = [] if o.group_wgrad else None
         # the block's six second-stage reductions (LayerNorm dgamma / dbeta x2, bias gradients, the fc2 dgrad's column sums) as
         # ONE launch at the end (ops.ReduceQueue); only with the grouped weight gradients, where every producer runs on this stream
-        rq = ops.ReduceQueue(dx2.device, _GROUP_SLOT[0], _GROUP_SLOT[1]) if (DEFER_REDUCE and jobs is not None) else None
+        rq = ops.ReduceQueue(dx2.device, _GROUP_SLOT[0], _GROUP_SLOT[1]) if o.defer_reduce else None
         # ---- MLP branch:  x2 = x1 + rs * fc2(gelu(fc1(LN2(x1))))
-        box = getattr(ctx, "box", None)
-        plan = getattr(ctx, "plan", None)            # stochastic-depth compaction of this block's MLP branch (see forward_gen)
-        if plan is not None and (rq is None or jobs is None):
-            raise RuntimeError("stochastic-depth compaction needs the grouped weight gradients + deferred reductions (its forward check)")
+        plan = ctx.plan                              # stochastic-depth compaction of this block's MLP branch (see forward_gen)
         live_mlp = plan[2] if plan is not None else m_live
-        handed = box.take(dx2) if box is not None else None
+        handed = ctx.box.take(dx2) if ctx.box is not None else None
         if handed is not None:
-            dy, dbias = handed                       # left by the next block's LayerNorm-1 backward (HANDOFF_CAST; on plan[0]'s rows)
+            dy, dbias = handed                       # left by the next block's LayerNorm-1 backward (the hand-off; on plan[0]'s rows)
         elif plan is not None:
             dy, dbias = ops.cast_rows_colsum(dx2, rs_mlp, act_dtype, gs, sv[11], rq=rq, perm=plan[0])
         else:
@@ -684,14 +678,12 @@ class TransformerBlockFn(torch.autograd.Function):
         da, dw2, db2, da_cs = yield from _linear_bwd_gen(dy, g, w2, hb_fc2, gelu_pre=a, m_live=live_mlp, db=dbias,
                                           dx_colsum=hb_fc1, gs=gs, dw_out=sv[10], db_out=sv[11],
                                           dxcs_out=sv[9], w_t=w2t, defer=jobs, aux_is_grad=light is None, rq=rq,
-                                          live_dense=plan is not None)   # da = (dy W2) * gelu'(a)
+                                          live_dense=plan is not None, side=o.side_stream)   # da = (dy W2) * gelu'(a)
         if light is not None:
             h2 = ops.layernorm_fwd(x1, n2w, light[1], light[2], act_dtype, mask, 0, want_stats=False, m_live=m_live)[0]
         dh2, dw1, db1 = yield from _linear_bwd_gen(da, h2, w1, hb_fc1, m_live=live_mlp, db=da_cs, gs=gs, dw_out=sv[8], db_out=sv[9], w_t=w1t,
-                                    defer=jobs, rq=rq, live_dense=plan is not None)
-        fuse_cast = (FUSE_LN_CAST and m_live is None and mask is None and act_dtype in ops.HALF_DTYPES
-                     and d % 256 == 0 and d <= 1024)
-        if fuse_cast:
+                                    defer=jobs, rq=rq, live_dense=plan is not None, side=o.side_stream)
+        if o.fuse_cast:
             # LN2's backward also writes the 16-bit, drop-path-scaled copy of dx1 (and its column sums = proj's bias
             # gradient) that the attention branch's backward starts from: no second pass over dx1
             dx1, dn2w, dn2b, dy, dbias = ops.layernorm_bwd_cast(
@@ -704,7 +696,7 @@ class TransformerBlockFn(torch.autograd.Function):
             # ---- attention branch:  x1 = x + rs * proj(attn(qkv(LN1(x))))
             dy, dbias = _scaled_cast_colsum(dx1, rs_attn, act_dtype, m_live, hb_proj, gs, cs_out=sv[5], rq=rq)
         dao, dwp, dbp = yield from _linear_bwd_gen(dy, ao, wp, hb_proj, m_live=m_live, db=dbias, gs=gs, dw_out=sv[4], db_out=sv[5], w_t=wpt,
-                                    defer=jobs, rq=rq)
+                                    defer=jobs, rq=rq, side=o.side_stream)
         dbq = None
         if hb_qkv and ops.attention_bwd_colsum_ok(qkv, t, hd, attn_saved):
             # the qkv bias gradient = colsum(dqkv) from the attention backward's own accumulators (one partial row per sequence),
@@ -715,37 +707,35 @@ class TransformerBlockFn(torch.autograd.Function):
         if light is not None:
             h1 = ops.layernorm_fwd(x2d, n1w, light[0], light[2], act_dtype, mask, 0, want_stats=False, m_live=m_live)[0]
         dh1, dwq, dbq = yield from _linear_bwd_gen(dqkv, h1, wq, hb_qkv, m_live=m_live, db=dbq, gs=gs, dw_out=sv[2], db_out=sv[3], w_t=wqt,
-                                    defer=jobs, rq=rq)
-        fb = getattr(ctx, "feeds_box", None)
-        ln_done = False
-        if jobs and WGRAD_LN and fb is not None and fuse_cast and not deferred and plan is None and fb.perm is None:
+                                    defer=jobs, rq=rq, side=o.side_stream)
+        fb = ctx.feeds_box
+        if o.wgrad_ln and fb is not None and plan is None and fb.perm is None:
             # (opt-in, round 4) the block's four weight gradients AND LayerNorm-1's backward as two ROLES of one launch on this stream:
             # the memory-bound rows on a quarter of the CUs beside the tiles on the rest (ops.gemm_wgrad_group_ln)
             dx, dn1w, dn1b, dy_below, db_below = ops.gemm_wgrad_group_ln(
                 jobs, m, 1.0 / gs, dh1, x2d, n1w, mean1, rstd1, dx1, fb.rowscale, fb.gs, dy_scale=1.0 / gs,
                 dgb_out=sink.ln_pair(0) if sink is not None else None, want_colsum=fb.has_bias, cs_out=fb.cs_out, rq=rq)
             fb.put(dx, dy_below, db_below)
-            ln_done = True
-        elif jobs:
-            # every dy exists: the block's four weight gradients in one launch.  Side stream (joined one block later)
-            # unless a gradient sink needs them at the end of THIS block
-            yield _WgradReq(jobs, m, 1.0 / gs, m_live, deferred, dx2.device)
-        if ln_done:
-            pass
-        elif fb is not None and fuse_cast:
-            # ... and hands the block BELOW the start of its backward (see HANDOFF_CAST): its drop-path row scale, its bias-gradient slot
-            dx, dn1w, dn1b, dy_below, db_below = ops.layernorm_bwd_cast(
-                dh1, x2d, n1w, mean1, rstd1, dx1, fb.rowscale, fb.gs, dy_scale=1.0 / gs,
-                dgb_out=sink.ln_pair(0) if sink is not None else None, want_colsum=fb.has_bias, cs_out=fb.cs_out, rq=rq,
-                cast_perm=fb.perm if rq is not None else None)
-            if fb.perm is None or rq is not None:
-                fb.put(dx, dy_below, db_below)       # (a compacted consumer without the parts form: it casts for itself)
         else:
-            dx, dn1w, dn1b = ops.layernorm_bwd(dh1, x2d, n1w, mean1, rstd1, mask, 0, dx_in=dx1, m_live=m_live,
-                                               dy_scale=1.0 / gs, dgb_out=sink.ln_pair(0) if sink is not None else None, rq=rq)
+            if jobs:
+                # every dy exists: the block's four weight gradients in one launch.  Side stream (joined one block later)
+                # unless a gradient sink needs them at the end of THIS block
+                yield _WgradReq(jobs, m, 1.0 / gs, m_live, o.defer_join, dx2.device, o.side_stream)
+            if fb is not None and o.fuse_cast:
+                # ... and hands the block BELOW the start of its backward (the hand-off, see _CastBox): its drop-path row scale, its
+                # bias-gradient slot
+                dx, dn1w, dn1b, dy_below, db_below = ops.layernorm_bwd_cast(
+                    dh1, x2d, n1w, mean1, rstd1, dx1, fb.rowscale, fb.gs, dy_scale=1.0 / gs,
+                    dgb_out=sink.ln_pair(0) if sink is not None else None, want_colsum=fb.has_bias, cs_out=fb.cs_out, rq=rq,
+                    cast_perm=fb.perm if rq is not None else None)
+                if fb.perm is None or rq is not None:
+                    fb.put(dx, dy_below, db_below)       # (a compacted consumer without the parts form: it casts for itself)
+            else:
+                dx, dn1w, dn1b = ops.layernorm_bwd(dh1, x2d, n1w, mean1, rstd1, mask, 0, dx_in=dx1, m_live=m_live, dy_scale=1.0 / gs,
+                                                   dgb_out=sink.ln_pair(0) if sink is not None else None, rq=rq)
         if rq is not None:
             rq.flush()                               # the block's partial rows -> dgamma / dbeta / bias gradients, one launch
-        if not deferred:
+        if not o.defer_join:
             join_side_stream(dx.device)              # the four weight gradients (side stream) are complete
         grads = (dn1w, dn1b, dwq, dbq, dwp, dbp, dn2w, dn2b, dw1, db1, dw2, db2)
         if sink is not None:
@@ -753,7 +743,15 @@ class TransformerBlockFn(torch.autograd.Function):
             # the bucket's all-reduce start now, under the rest of the backward
             grads = tuple(None if v is not None else g_ for g_, v in zip(grads, sv))
             sink.done()
-        return (dx.view(xshape),) + grads + (None,) * 18
+        return (dx.view(xshape),) + grads + (None,) * 17
+
+
+def block_call(x, params, heads, eps, act_dtype, *, mask=None, probs_out=None, rowscale_attn=None, rowscale_mlp=None, cu=None,
+               max_t=None, m_live=None, qk_scale=None, sink=None, pend_branch=None, pend_rs=None, defer_out=False, branch16=False,
+               drop_plan=None):
+    """forward_gen's positional arguments (for TransformerBlockFn.apply / GroupedBlocksFn) from a block's 12 parameters and its options BY NAME"""
+    return (x, *params, mask, probs_out, heads, eps, act_dtype, rowscale_attn, rowscale_mlp, cu, max_t, m_live, qk_scale, sink,
+            pend_branch, pend_rs, defer_out, branch16, drop_plan)
 
 
 GROUP_BLOCKS = os.environ.get("EDITOR_GROUP_BLOCKS", "1") != "0"      # A/B switch: GroupedBlocksFn for the HMA modality blocks
@@ -805,7 +803,7 @@ class GroupedBlocksFn(torch.autograd.Function):
 def _scaled_cast_colsum(dx, rowscale, dtype, m_live, want_colsum, gs=1.0, cs_out=None, rq=None):
     """_scaled_cast, plus the (unscaled) column sums of the result when the consumer has a bias (dense 16-bit rows only)."""
     if (want_colsum and m_live is None and dtype in ops.HALF_DTYPES and dx.dtype == torch.float32
-            and dx.shape[1] % 256 == 0 and dx.shape[1] <= 1024):
+            and _row_kernel_width(dx.shape[1])):
         return ops.cast_rows_colsum(dx, rowscale, dtype, gs, cs_out, rq=rq)
     return _scaled_cast(dx, rowscale, dtype, m_live, gs), None
 

@@ -461,11 +461,11 @@ class EDITOR(nn.Module):
                     plan = (plans[0][i, 1], plans[1][i, 1], plans[2][i, 1:2])       # MLP branch: (perm, inv, live rows)
             last = i == len(base.blocks) - 1
             defer = self.branch16 and not last        # (the last block adds its own fc2 branch: the final norm takes plain rows)
-            out = fn.TransformerBlockFn.apply(x, *_block_args(blk.norm1, blk.attn, blk.norm2, blk.mlp), None,
-                                              probs if recompute else probs[i], base.heads, 1e-6,
-                                              self.fn_dtype_last if last else self.fn_dtype, rs_a, rs_m,
-                                              None, None, None, base.qk_scale, self._sink("backbone.%d" % i),
-                                              pend_branch, pend_rs, defer, self.branch16, plan)
+            out = fn.TransformerBlockFn.apply(*fn.block_call(
+                x, _block_args(blk.norm1, blk.attn, blk.norm2, blk.mlp), base.heads, 1e-6,
+                self.fn_dtype_last if last else self.fn_dtype, probs_out=probs if recompute else probs[i], rowscale_attn=rs_a,
+                rowscale_mlp=rs_m, qk_scale=base.qk_scale, sink=self._sink("backbone.%d" % i), pend_branch=pend_branch,
+                pend_rs=pend_rs, defer_out=defer, branch16=self.branch16, drop_plan=plan))
             if defer:
                 x, pend_branch = out
                 pend_rs = rs_m
@@ -502,17 +502,15 @@ class EDITOR(nn.Module):
         for i, tag in enumerate(m_[2] for m_ in self.modalities):
             args = _block_args(getattr(fb, "norm" + tag), getattr(fb, "attn" + tag), getattr(fb, "norm" + tag + "_"),
                                getattr(fb, "mlp" + tag))
-            mods.append(fn.TransformerBlockFn.apply(feats_mod[i], *args, mask, None, self.hma_heads, 1e-5,
-                                                    self.fn_dtype_hma, None, None, None, None, None, None,
-                                                    self._sink("hma." + tag)))
+            mods.append(fn.TransformerBlockFn.apply(*fn.block_call(feats_mod[i], args, self.hma_heads, 1e-5, self.fn_dtype_hma,
+                                                                   mask=mask, sink=self._sink("hma." + tag))))
         loss_ocfr = None
         if self.training:
             loss_ocfr = self._ocfr([m_[:, 0] for m_ in mods], label)
         x = torch.cat(mods, dim=1)
         mask3 = mask.repeat(1, nmod).contiguous()
-        x = fn.TransformerBlockFn.apply(x, *_block_args(fb.norm1, fb.attn1, fb.norm2, fb.mlp), mask3, None,
-                                        self.hma_heads, 1e-5, self.fn_dtype_hma, None, None, None, None, None, None,
-                                        self._sink("hma.joint"))
+        x = fn.TransformerBlockFn.apply(*fn.block_call(x, _block_args(fb.norm1, fb.attn1, fb.norm2, fb.mlp), self.hma_heads, 1e-5,
+                                                       self.fn_dtype_hma, mask=mask3, sink=self._sink("hma.joint")))
         x = fn.LayerNormFn.apply(x, fb.out_norm.weight, fb.out_norm.bias, 1e-5, mask3.view(-1))
         return x, loss_ocfr
 
@@ -531,8 +529,8 @@ class EDITOR(nn.Module):
         for i, tag in enumerate(m_[2] for m_ in self.modalities):
             args = _block_args(getattr(fb, "norm" + tag), getattr(fb, "attn" + tag), getattr(fb, "norm" + tag + "_"),
                                getattr(fb, "mlp" + tag))
-            flat.append((xa_mod[i], *args, plan.mask_a, None, self.hma_heads, 1e-5, self.fn_dtype_hma, None, None, plan.cu, t,
-                         plan.live_a, None, self._sink("hma." + tag)))
+            flat.append(fn.block_call(xa_mod[i], args, self.hma_heads, 1e-5, self.fn_dtype_hma, mask=plan.mask_a, cu=plan.cu,
+                                      max_t=t, m_live=plan.live_a, sink=self._sink("hma." + tag)))
         if fn.GROUP_BLOCKS and self.fn_dtype_hma in ops.HALF_DTYPES and not self.act_light:
             # the per-modality blocks are identical in shape and independent: one node, their products as grouped launches
             # (round 4: ~7 400 live rows per modality are 87 tiles of a 768-wide product - a third of a round of the 256 CUs)
@@ -546,9 +544,9 @@ class EDITOR(nn.Module):
             loss_ocfr = self._ocfr(list(cls.view(nmod, b, d).unbind(0)), label)
         else:
             xb = fn.GatherRowsFn.apply(xa, plan.map_b, plan.live_a, nmod, plan.mb)
-        xb = fn.TransformerBlockFn.apply(xb, *_block_args(fb.norm1, fb.attn1, fb.norm2, fb.mlp), plan.mask_b, None,
-                                         self.hma_heads, 1e-5, self.fn_dtype_hma, None, None, plan.cu3, nmod * t, plan.live_b,
-                                         None, self._sink("hma.joint"))
+        xb = fn.TransformerBlockFn.apply(*fn.block_call(
+            xb, _block_args(fb.norm1, fb.attn1, fb.norm2, fb.mlp), self.hma_heads, 1e-5, self.fn_dtype_hma, mask=plan.mask_b,
+            cu=plan.cu3, max_t=nmod * t, m_live=plan.live_b, sink=self._sink("hma.joint")))
         xb = fn.LayerNormFn.apply(xb, fb.out_norm.weight, fb.out_norm.bias, 1e-5, plan.mask_b, plan.live_b)
         pooled, num = fn.PoolPackedFn.apply(xb, plan.cu, b, nmod, plan.live_b)
         self.last_aux["plan"] = plan

@@ -616,6 +616,122 @@ def test_layernorm1_backward_as_a_role_of_the_weight_gradient_launch(dtype):
                 assert rel_err(bb, a) < 2e-3, (n, rel_err(bb, a))
 
 
+_CHAINS = {}
+
+
+def _planned_chain(dtype):
+    """Three chained backbone blocks (64 x 129 token rows, d = 768) with per-sample drop-path scales on both branches and a
+    stochastic-depth plan for each MLP branch -> (run, reference).  run(between) = forward, `between()`, backward -> (output, input
+    gradient, parameter gradients); the reference is run(nothing), computed once per dtype and shared."""
+    if dtype in _CHAINS:
+        return _CHAINS[dtype]
+    from editor_amd import functional as fn, ops
+    from editor_amd.modeling.make_model import _block_args
+    m, cfg, c, cams = _model("RGBNT201", 11, dtype, drop_path=0.1)
+    base = m.BACKBONE.base
+    blocks = list(base.blocks)[:3]
+    act, heads, qk_scale = m.fn_dtype, base.heads, base.qk_scale
+    del m, base                                                       # (the closure below keeps the three blocks only)
+    b, tk, d, hidden = 64, 129, 768, 3072
+    rows, live_samples = b * tk, 48
+    # the input condition of these tests, on the CPU before anything runs: the grouped weight gradients reduce over ceil64(live)
+    # rows, the MLP products write ceil_TH(live) of them - every row that is read has been written
+    th = ops.gemm_tile_rows(rows, hidden)
+    live_rows = live_samples * tk
+    assert live_rows == 6192 and -(-live_rows // 64) * 64 <= -(-live_rows // th) * th, (live_rows, th)
+    assert rows >= 2048 and rows % 64 == 0
+    g = torch.Generator().manual_seed(21)
+    keeps = torch.zeros(3, 2, b, dtype=torch.bool)
+    for i in range(3):
+        keeps[i, 0, torch.randperm(b, generator=g)[:56]] = True               # attention branch: 56 of 64 samples kept
+        keeps[i, 1, torch.randperm(b, generator=g)[:live_samples]] = True     # MLP branch: 48 of 64
+    sc = (keeps.float() / 0.9).unsqueeze(-1).expand(3, 2, b, tk).reshape(3, 2, rows).contiguous().cuda()
+    perm, inv, live = ops.droppath_plan(sc, 3, b, tk)
+    assert [int(live[i, 1]) for i in range(3)] == [live_rows] * 3
+    x0 = torch.randn(b, tk, d, generator=g).cuda()
+    w_out = (torch.randn(b, tk, d, generator=g) * 1e-3).cuda()       # (f16: the gradients travel loss-scaled - keep them in range)
+    compacted = [0]
+    real_perm = ops.layernorm_fwd_perm
+
+    def counted(*a, **k):
+        compacted[0] += 1
+        return real_perm(*a, **k)
+
+    def run(between):
+        for blk in blocks:
+            for p in blk.parameters():
+                p.grad = None
+        compacted[0] = 0
+        ops.layernorm_fwd_perm = counted
+        try:
+            x = x0.clone().requires_grad_(True)
+            h = x
+            for i, blk in enumerate(blocks):
+                h = fn.TransformerBlockFn.apply(h, *_block_args(blk.norm1, blk.attn, blk.norm2, blk.mlp), None, None, heads, 1e-6,
+                                                act, sc[i, 0], sc[i, 1], None, None, None, qk_scale, None, None, None,
+                                                False, False, (perm[i, 1], inv[i, 1], live[i, 1:2]))
+        finally:
+            ops.layernorm_fwd_perm = real_perm
+        assert compacted[0] == 3, ("compacted MLP branches that ran", compacted[0])
+        between()
+        (h * w_out).sum().backward()
+        torch.cuda.synchronize()
+        return h.detach().clone(), x.grad.clone(), [p.grad.clone() for blk in blocks for p in blk.parameters()]
+
+    names = [n for i, blk in enumerate(blocks) for n, _ in blk.named_parameters(prefix="blocks.%d" % i)]
+    ref = run(lambda: None)
+    assert torch.isfinite(ref[1]).all() and float(ref[1].abs().max()) > 0
+    assert all(bool(torch.isfinite(v).all()) and float(v.abs().max()) > 0 for v in ref[2])
+    _CHAINS[dtype] = (run, ref, names)
+    return _CHAINS[dtype]
+
+
+def _same_as_reference(ref, got, names, what):
+    assert torch.equal(ref[0], got[0]), what
+    assert torch.equal(ref[1], got[1]), (what, float((ref[1] - got[1]).abs().max()))
+    for n, a, bb in zip(names, ref[2], got[2]):
+        assert torch.equal(a, bb), (what, n, float((a - bb).abs().max()), float(a.abs().max()))
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "f16"])
+def test_block_backward_uses_what_its_forward_decided(dtype):
+    """A block's backward branches on the record its forward made (functional._decide_block), not on the module switches as they
+    stand at backward time: with one switch inverted between the forward and `.backward()` - each of the switches the two halves
+    used to read separately - the block output, the input gradient and every parameter gradient equal the untouched run bit for
+    bit (before, a flipped GROUP_WGRAD / DEFER_REDUCE raised and a flipped FUSE_LN_CAST silently ran LayerNorm-2's plain backward
+    on compacted rows)."""
+    from editor_amd import functional as fn
+    run, ref, names = _planned_chain(dtype)
+    assert fn.DROP_SKIP
+    for switch in ("GROUP_WGRAD", "DEFER_REDUCE", "FUSE_LN_CAST", "HANDOFF_CAST", "DGRAD_KMAJOR", "WGRAD_DEFER_JOIN", "DROP_SKIP",
+                   "ACT_LIGHT"):
+        old = getattr(fn, switch)
+
+        def flip():
+            setattr(fn, switch, not old)
+        try:
+            got = run(flip)
+            assert getattr(fn, switch) == (not old)
+        finally:
+            setattr(fn, switch, old)
+        _same_as_reference(ref, got, names, switch)
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "f16"])
+def test_second_models_options_do_not_reach_a_pending_backward(dtype):
+    """functional.set_model_options for ANOTHER model (another loss scale, activation-light blocks) between a chain's forward and its
+    backward: the pending backward keeps what its forward captured - same bits as the untouched run."""
+    from editor_amd import functional as fn
+    run, ref, names = _planned_chain(dtype)
+    old = (fn.F16_GRAD_SCALE, fn.ACT_LIGHT)
+    try:
+        got = run(lambda: fn.set_model_options(grad_scale_f16=1.0, act_light=True))
+        assert (fn.F16_GRAD_SCALE, fn.ACT_LIGHT) == (1.0, True)
+    finally:
+        fn.set_model_options(grad_scale_f16=old[0], act_light=old[1])
+    _same_as_reference(ref, got, names, "set_model_options")
+
+
 def test_hipgraph_replay_matches_eager_training():
     """The whole training step (forward, HIP loss head, backward with the side-stream weight gradients, fused SGD with
     drop-path) captured into a hipGraph and replayed == the same number of eager steps: identical kernels on identical

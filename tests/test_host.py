@@ -119,3 +119,130 @@ def test_generated_doc_blocks_are_current():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cp = subprocess.run([sys.executable, os.path.join(root, "tools", "doc_numbers.py"), "--check"], stdout=subprocess.PIPE, text=True)
     assert cp.returncode == 0, cp.stdout
+
+
+# ---- functional._decide_block: one decision record per transformer block, made at forward time --------------------------------
+_SWITCH_DEFAULTS = dict(DROP_SKIP=True, ACT_LIGHT=False, GROUP_WGRAD=True, DEFER_REDUCE=True, FUSE_LN_CAST=True, HANDOFF_CAST=True,
+                        DGRAD_KMAJOR=True, WGRAD_SIDE_STREAM=True, WGRAD_DEFER_JOIN=True, WGRAD_LN=False, FWD_GRAD=True,
+                        F16_GRAD_SCALE=32768.0)
+_DECISIONS = ("light", "plan_ok", "group_wgrad", "defer_reduce", "fuse_cast", "handoff", "kmajor", "side_stream", "defer_join",
+              "wgrad_ln")
+_BACKBONE = dict(has_rowscale_mlp=True, has_sink=True)                      # a dense backbone block under drop-path, gradient sinks on
+_ROW_A = dict(plan_ok=True, group_wgrad=True, defer_reduce=True, fuse_cast=True, handoff=True, kmajor=True, side_stream=True,
+              defer_join=True)
+
+
+@pytest.fixture
+def block_switches(monkeypatch):
+    """editor_amd.functional with every switch _decide_block reads at its default, whatever the environment set"""
+    from editor_amd import functional as fn
+    for k, v in _SWITCH_DEFAULTS.items():
+        monkeypatch.setattr(fn, k, v)
+    return fn
+
+
+def _decisions(fn, dtype, m, d, hidden=None, **kw):
+    o = fn._decide_block(dtype, m, d, 4 * d if hidden is None else hidden, **kw)
+    assert all(isinstance(getattr(o, k), bool) for k in _DECISIONS + ("half", "save_aux"))
+    return o, {k for k in _DECISIONS if getattr(o, k)}
+
+
+def _on(**kw):
+    return {k for k, v in kw.items() if v}
+
+
+def test_decide_block_table(block_switches, monkeypatch):
+    """The decisions of a block's forward AND backward for the shapes the models run, read off the predicates the two generators applied
+    separately before (plan check, grouped weight gradients, deferred reductions, fused LayerNorm casts, hand-off, k-major dgrads,
+    side stream, deferred join).  Hidden = 4 d."""
+    fn = block_switches
+    bf16 = torch.bfloat16
+    # a: the bench workload's backbone block (3 x 128 x 129 token rows)
+    o, got = _decisions(fn, bf16, 49536, 768, **_BACKBONE)
+    assert got == _on(**_ROW_A) and o.half and o.save_aux and o.gs == 1.0
+    # b: 3 x 16 x 211 rows - not a multiple of 64
+    o, got = _decisions(fn, bf16, 10128, 768, **_BACKBONE)
+    assert got == {"fuse_cast", "handoff", "kmajor", "side_stream"}
+    # c: a compacted HMA block (packed sequences, row mask, live-row count)
+    o, got = _decisions(fn, bf16, 7424, 768, has_cu=True, has_mask=True, has_m_live=True, has_sink=True)
+    assert {"group_wgrad", "defer_reduce", "kmajor"} <= got and not got & {"plan_ok", "fuse_cast", "handoff"}
+    assert got == {"group_wgrad", "defer_reduce", "kmajor", "side_stream", "defer_join"}
+    # d: a width the 256-wide tiles / row kernels do not take
+    o, got = _decisions(fn, bf16, 49536, 384, **_BACKBONE)
+    assert got == {"kmajor", "side_stream"}
+    # e: few rows - nothing that is keyed on m >= 2048
+    o, got = _decisions(fn, bf16, 1032, 768, **_BACKBONE)
+    assert got == {"fuse_cast", "handoff"}
+    # f: the fp32 parity mode decides nothing (and always keeps the pre-activation)
+    for m, d in ((49536, 768), (10128, 768), (1032, 384)):
+        o, got = _decisions(fn, torch.float32, m, d, **_BACKBONE)
+        assert got == set() and not o.half and o.gs == 1.0 and o.save_aux
+    # g: activation-light blocks take no plan
+    monkeypatch.setattr(fn, "ACT_LIGHT", True)
+    o, got = _decisions(fn, bf16, 49536, 768, **_BACKBONE)
+    assert got == _on(**dict(_ROW_A, plan_ok=False, light=True))
+    o, got = _decisions(fn, fn.F16X2H, 49536, 768, **_BACKBONE)          # the head-only split block follows the switch ...
+    assert got == _on(**dict(_ROW_A, plan_ok=False, light=True))
+    o, got = _decisions(fn, fn.F16X2, 49536, 768, **_BACKBONE)           # ... the all-split block saves its hi halves as they are
+    assert got == _on(**dict(_ROW_A, plan_ok=False))
+    monkeypatch.setattr(fn, "ACT_LIGHT", False)
+    # g': the split-precision forward plans as f16 and its (f16) backward travels loss-scaled
+    for marker in (fn.F16X2, fn.F16X2H):
+        o, got = _decisions(fn, marker, 49536, 768, **_BACKBONE)
+        assert got == _on(**_ROW_A) and o.half and o.gs == fn.F16_GRAD_SCALE == 32768.0
+    o, got = _decisions(fn, torch.float16, 49536, 768, **_BACKBONE)
+    assert got == _on(**_ROW_A) and o.gs == 32768.0
+    # h: each switch the plan rests on, off alone: no plan, and that switch's own decision (with what follows from it) off
+    for switch, off in (("GROUP_WGRAD", {"group_wgrad", "defer_reduce", "defer_join"}), ("DEFER_REDUCE", {"defer_reduce"}),
+                        ("FUSE_LN_CAST", {"fuse_cast", "handoff"}), ("DROP_SKIP", set())):
+        monkeypatch.setattr(fn, switch, False)
+        o, got = _decisions(fn, bf16, 49536, 768, **_BACKBONE)
+        assert got == _on(**_ROW_A) - {"plan_ok"} - off, switch
+        monkeypatch.setattr(fn, switch, True)
+    # the remaining switches and conditions, one at a time
+    for switch, off in (("HANDOFF_CAST", {"handoff"}), ("DGRAD_KMAJOR", {"kmajor"}), ("WGRAD_DEFER_JOIN", {"defer_join"}),
+                        ("WGRAD_SIDE_STREAM", {"side_stream", "defer_join"})):
+        monkeypatch.setattr(fn, switch, False)
+        o, got = _decisions(fn, bf16, 49536, 768, **_BACKBONE)
+        assert got == _on(**_ROW_A) - off, switch
+        monkeypatch.setattr(fn, switch, True)
+    o, got = _decisions(fn, bf16, 49536, 768, has_rowscale_mlp=True)       # no gradient sinks: joined inside the block
+    assert got == _on(**_ROW_A) - {"defer_join"}
+    monkeypatch.setattr(fn, "WGRAD_LN", True)                              # the opt-in role launch: only where nothing is deferred
+    assert _decisions(fn, bf16, 49536, 768, has_rowscale_mlp=True)[1] == _on(**_ROW_A) - {"defer_join"} | {"wgrad_ln"}
+    assert _decisions(fn, bf16, 49536, 768, **_BACKBONE)[1] == _on(**_ROW_A)
+    monkeypatch.setattr(fn, "WGRAD_LN", False)
+    o, got = _decisions(fn, bf16, 49536, 768, has_sink=True)               # no drop-path scale on the MLP branch: nothing to skip
+    assert got == _on(**_ROW_A) - {"plan_ok"}
+    for kw in (dict(branch16=True), dict(defer_out=True, branch16=True), dict(has_pend=True, branch16=True)):
+        o, got = _decisions(fn, bf16, 49536, 768, **_BACKBONE, **kw)       # 16-bit branch outputs: no plan, no hand-off
+        assert got == _on(**_ROW_A) - {"plan_ok", "handoff"}, kw
+    # the GELU derivative is saved when a backward can follow (16-bit modes; the forward saw the grad mode on)
+    assert not _decisions(fn, bf16, 49536, 768, can_backward=False)[0].save_aux
+    monkeypatch.setattr(fn, "FWD_GRAD", False)
+    assert not _decisions(fn, bf16, 49536, 768)[0].save_aux and _decisions(fn, torch.float32, 49536, 768)[0].save_aux
+
+
+def test_block_call_fills_forward_gens_positionals():
+    """functional.block_call hands TransformerBlockFn.apply exactly forward_gen's positional list: as many entries as it has parameters
+    after ctx, every named option in its slot, and an option left out as the parameter's own default."""
+    from editor_amd import functional as fn
+    sig = list(inspect.signature(fn.TransformerBlockFn.forward_gen).parameters.values())[1:]
+    names = [p.name for p in sig]
+    params = ["p%d" % i for i in range(12)]
+    bare = fn.block_call("x", params, 12, 1e-6, "dt")
+    assert len(bare) == len(sig) == 30
+    assert bare[:13] == ("x", *params) and names[0] == "x" and names[1:13] == "n1w n1b qkvw qkvb projw projb n2w n2b fc1w fc1b fc2w fc2b".split()
+    given = dict(heads=12, eps=1e-6, act_dtype="dt")
+    for p, v in zip(sig[13:], bare[13:]):
+        if p.name in given:
+            assert v == given[p.name], p.name
+        elif p.default is inspect.Parameter.empty:
+            assert v is None, p.name                      # (mask, probs_out, the row scales: forward_gen has no default for them)
+        else:
+            assert v is p.default or v == p.default, p.name
+    opts = [n for n in names[13:] if n not in given]
+    kwonly = [p.name for p in inspect.signature(fn.block_call).parameters.values() if p.kind is inspect.Parameter.KEYWORD_ONLY]
+    assert sorted(opts) == sorted(kwonly)
+    full = fn.block_call("x", params, 12, 1e-6, "dt", **{n: "<%s>" % n for n in opts})
+    assert [full[names.index(n)] for n in opts] == ["<%s>" % n for n in opts]

@@ -16,8 +16,11 @@
 //                          THE path's kernel - every forward, dgrad and (one round of split-K workgroups) wgrad product of
 //                          the transformer blocks, 208-row short tiles for the 768-wide outputs, and the split-precision
 //                          (hi.hi + hi.lo + lo.hi) forward of the 'f16x2' mode
-//   gemm_bf16_pipe_kernel  256x128x64, three LDS-DMA stages: shapes the ping-pong kernel does not take
-//   gemm_bf16_kernel       128x128x64, 4 waves, register- or DMA-staged: small / ragged problems (K % 64 != 0, N < 128)
+//   gemm_bf16_pipe_kernel  256x128x64, three LDS-DMA stages: M >= 256, N >= 128, K % 64 == 0 that does not go to the ping-pong kernel
+//   gemm_bf16_kernel       128x128x64, 4 waves, register- or DMA-staged: small / ragged problems (K % 64 != 0, M < 256, N < 128)
+// Which one runs is decided by the host code at the end of this file, from three predicates written once there: pp_takes (the
+// ping-pong kernel can run it: M, N >= 256, K % 64 == 0), pp_big (it goes there by itself: M >= 2048, N >= 512, A k-major, one split)
+// and pp_staged_ok (its one-pass 16-byte epilogue: N, ldc, ldaux % 8 == 0, one split, beta 0 - short tiles, row maps, column sums).
 // XCD-aware tile order (consecutive n-tiles of one A row-panel stay on one XCD's L2); split-K through per-split slabs and a
 // fixed-order reduction (deterministic), fp32 atomics only on the generic kernel.
 #include "common.h"
@@ -1742,12 +1745,49 @@ int launch_pipe_t(GemmB16Args g, hipStream_t stream)
     return 0;
 }
 
+// ping-pong body: >= 2 K-tile buffers, the fp32 half-tile image, the bf16 tile image + GELU table
+constexpr int kPpLdsBytes = 256 * (256 * 2 + 16) + (int)kLutBytes;
+
+// Every GemmB16Args starts here, all options off; each site then names the fields its path turns on.
+inline GemmB16Args gemm_args(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, long ldc, float alpha)
+{
+    GemmB16Args g{};
+    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.C = C; g.M = M; g.N = N; g.K = K;
+    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.alpha = alpha;
+    return g;
+}
+
+// The C ABI's option word, taken apart once; `epilogue` keeps the base value, and with it any bit of no option (refused as a base).
+struct EpiOptions { int base; bool colsum, force_pp, aux_grad, pipe128; int tile_frags, stagger; };   // (tile rows / 16; cycles)
+inline EpiOptions decode_epilogue(int& epilogue)
+{
+    const int w = epilogue;
+    epilogue &= ~(EDITOR_EPI_COLSUM | EDITOR_EPI_FORCE_PP | EDITOR_EPI_AUX_GRAD | EDITOR_EPI_PIPE128 | 0xF000 | EDITOR_EPI_STAGGER(63));
+    return {epilogue, (w & EDITOR_EPI_COLSUM) != 0, (w & EDITOR_EPI_FORCE_PP) != 0, (w & EDITOR_EPI_AUX_GRAD) != 0,
+            (w & EDITOR_EPI_PIPE128) != 0, (w >> 12) & 15, ((w >> 17) & 63) * 2048};
+}
+
+// The ping-pong kernel can run it: whole K-tiles (LDS-DMA staging), a 256 x 256 tile's worth of rows and columns.
+inline bool pp_takes(int M, int N, int K) { return M >= 256 && N >= 256 && K % BK == 0; }
+// It goes there by itself, column sums included: faster than the 256x128 kernel from 16 full tiles; a row-k A only when forced.
+// (split <= 1 is "one split" for the raw argument, which may be 0, and for the clamped one, >= 1, alike)
+inline bool pp_big(int M, int N, int K, bool ak, int split) { return pp_takes(M, N, K) && M >= 2048 && N >= 512 && ak && split <= 1; }
+// Its one-pass staged epilogue (short tiles, row maps, column sums, 32x32 MFMAs): whole 16-byte lines, no beta, no later split.
+inline bool pp_staged_ok(int N, long ldc, long ldx, int split, float beta) { return !((N | ldc | ldx) & 7) && split <= 1 && beta == 0.f; }
+
+// run-time choices -> template arguments (bool_constant values); dtype 1 = bf16, 2 = f16, else refused
+template <class Fn> int with_bool(bool b, Fn&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <class Fn> int with_h16(int dt, Fn&& f) { return dt == 1 || dt == 2 ? with_bool(dt == 2, f) : (int)hipErrorInvalidValue; }
+template <class Fn> int with_layout(bool ak, bool bk, bool cf, Fn&& f)
+{
+    return with_bool(ak, [&](auto a) { return with_bool(bk, [&](auto b) { return with_bool(cf, [&](auto c) { return f(a, b, c); }); }); });
+}
+
 template <bool F16, bool AK, bool BK_, bool CF, int F0, int F1, bool SPLIT = false, bool MI32 = false>
 int launch_pp_t(GemmB16Args g, hipStream_t stream)
 {
-    constexpr int LDS = 256 * (256 * 2 + 16) + (int)kLutBytes;  // >= 2 K-tile buffers, the fp32 half-tile image, the bf16 tile image + GELU table
     auto kern = gemm_bf16_pp_kernel<F16, AK, BK_, CF, F0, F1, SPLIT, MI32>;
-    if (int e = ensure_lds<gemm_bf16_pp_kernel<F16, AK, BK_, CF, F0, F1, SPLIT, MI32>>(LDS)) return e;
+    if (int e = ensure_lds<gemm_bf16_pp_kernel<F16, AK, BK_, CF, F0, F1, SPLIT, MI32>>(kPpLdsBytes)) return e;
     g.tiles_m = (g.M + (F0 + F1) * 16 - 1) / ((F0 + F1) * 16);
     g.tiles_n = (g.N + 255) / 256;
     // measured: the LDS-staged epilogue (full-line 16-byte stores) beats the direct one on every layout here
@@ -1769,7 +1809,7 @@ int launch_pp_t(GemmB16Args g, hipStream_t stream)
             hipError_t e1 = hipMemsetAsync(buf, 0, sizeof(unsigned long long) * 8 * nwg, stream);
             if (e1 != hipSuccess) return (int)e1;
             g.trace = buf;
-            hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, g.splitk), dim3(512), LDS, stream, g);
+            hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, g.splitk), dim3(512), kPpLdsBytes, stream, g);
             if ((e1 = hipStreamSynchronize(stream)) != hipSuccess) return (int)e1;
             static unsigned long long host[8 * 65536];
             if ((e1 = hipMemcpy(host, buf, sizeof(unsigned long long) * 8 * nwg, hipMemcpyDeviceToHost)) != hipSuccess) return (int)e1;
@@ -1788,7 +1828,7 @@ int launch_pp_t(GemmB16Args g, hipStream_t stream)
         }
     }
 #endif
-    hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, g.splitk), dim3(512), LDS, stream, g);
+    hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, g.splitk), dim3(512), kPpLdsBytes, stream, g);
     EDITOR_LAUNCH_CHECK();
     return 0;
 }
@@ -1802,7 +1842,7 @@ int launch_pp(const GemmB16Args& g, hipStream_t stream)
 #if EDITOR_PP_MI32
         // full tiles, 16-bit output through the one-pass staged epilogue (the conditions pp_body's `staged` path tests): 32x32x16 MFMAs
         if constexpr (!CF) {
-            if (g.beta == 0.f && g.splitk == 1 && (g.N & 7) == 0 && (g.ldc & 7) == 0 && (g.ldaux & 7) == 0 &&
+            if (pp_staged_ok(g.N, g.ldc, g.ldaux, g.splitk, g.beta) &&
                 (g.epilogue == EDITOR_EPI_NONE || g.epilogue == EDITOR_EPI_GELU || g.epilogue == EDITOR_EPI_GELU_BWD))
                 return launch_pp_t<F16, AK, BK_, CF, 8, 8, false, true>(g, stream);
         }
@@ -1826,8 +1866,8 @@ int launch_pipe(const GemmB16Args& g, hipStream_t stream)
 #endif
     // EDITOR_EPI_PIPE128 (the caller's tile-count heuristic, editor_amd.ops.gemm): few token rows - the strong-scaling series'
     // B_local = 16 gives M = 6 192, i.e. 72 - 90 tiles of a 768-wide output on 256 CUs - take the 256x128 tiles instead
-    const bool pp_auto = g.M >= 2048 && g.splitk == 1 && AK && g.N >= 512 && !g.prefer_pipe;
-    if (g.N >= 256 && (pp_mode == 1 || g.colsum || (pp_mode < 0 && pp_auto))) return launch_pp<F16, AK, BK_, CF>(g, stream);
+    const bool pp_auto = pp_big(g.M, g.N, g.K, AK, g.splitk) && !g.prefer_pipe;
+    if (pp_takes(g.M, g.N, g.K) && (pp_mode == 1 || g.colsum || (pp_mode < 0 && pp_auto))) return launch_pp<F16, AK, BK_, CF>(g, stream);
     return launch_pipe_t<F16, AK, BK_, CF, 256, 128, 3, 8>(g, stream);
 }
 
@@ -1846,23 +1886,16 @@ int gemm_h16(const uint16_t* A, const uint16_t* B, void* C, int c_f32, int M, in
     if (transB && (N & 7)) return (int)hipErrorInvalidValue;
     if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(C)) & 15)
         return (int)hipErrorInvalidValue;
-    const bool want_colsum = (epilogue & EDITOR_EPI_COLSUM) != 0;
-    const bool force_pp = (epilogue & EDITOR_EPI_FORCE_PP) != 0;
-    const bool aux_grad = (epilogue & EDITOR_EPI_AUX_GRAD) != 0;
-    const int tile_frags = (epilogue >> 12) & 15;                       // EDITOR_EPI_TILE_ROWS(h): h / 16, 0 = full tiles
-    if (tile_frags != 0 && tile_frags != 13) return (int)hipErrorInvalidValue;
-    const bool prefer_pipe = (epilogue & EDITOR_EPI_PIPE128) != 0 && !want_colsum && !force_pp && tile_frags == 0;
-    const int stagger = ((epilogue >> 17) & 63) * 2048;                 // EDITOR_EPI_STAGGER(c)
-    epilogue &= ~(EDITOR_EPI_COLSUM | EDITOR_EPI_FORCE_PP | EDITOR_EPI_AUX_GRAD | EDITOR_EPI_PIPE128 | 0xF000 | EDITOR_EPI_STAGGER(63));
-    if (aux_grad && epilogue != EDITOR_EPI_GELU && epilogue != EDITOR_EPI_GELU_BWD) return (int)hipErrorInvalidValue;
-    if (want_colsum && (c_f32 || epilogue == EDITOR_EPI_RESIDUAL || splitk > 1 || !splitk_ws || transA || M < 2048 || N < 512 ||
-                        (N & 7) || (ldc & 7) || (ldaux & 7) || (K % BK) || beta != 0.f))
+    const EpiOptions o = decode_epilogue(epilogue);              // (every option accepted)
+    if (o.tile_frags != 0 && o.tile_frags != 13) return (int)hipErrorInvalidValue;
+    if (o.aux_grad && epilogue != EDITOR_EPI_GELU && epilogue != EDITOR_EPI_GELU_BWD) return (int)hipErrorInvalidValue;
+    const bool staged = pp_staged_ok(N, ldc, ldaux, splitk, beta);
+    if (o.colsum && (c_f32 || epilogue == EDITOR_EPI_RESIDUAL || !splitk_ws || !pp_big(M, N, K, !transA, splitk) || !staged))
         return (int)hipErrorInvalidValue;                        // the column sums exist in the one-pass 256x256 epilogue only
     // (with m_live: the tiles beyond the live rows zero their partial row, the rows of the last live tile beyond *m_live are
     //  the caller's zero rows by contract - stochastic-depth compaction, editor_droppath_plan)
-    if (rowmap && (!c_f32 || (epilogue & 0xFF) != EDITOR_EPI_RESIDUAL || transA || transB || splitk > 1 || (N & 7) || (ldc & 7) ||
-                   (ldaux & 7) || (K % BK) || beta != 0.f || M < 256 || N < 256))
-        return (int)hipErrorInvalidValue;                        // row scatter: the staged fp32 residual epilogue of the 256x256 kernel
+    if (rowmap && (!c_f32 || (epilogue & 0xFF) != EDITOR_EPI_RESIDUAL || transA || transB || !pp_takes(M, N, K) || !staged))
+        return (int)hipErrorInvalidValue;                        // row scatter: the staged fp32 residual epilogue, forced
     // (aux may be NULL for EDITOR_EPI_GELU: a no-grad forward - model.eval() / do_inference - saves nothing for a backward)
     if (epilogue != EDITOR_EPI_NONE && ((!aux && epilogue != EDITOR_EPI_GELU) || (ldaux & 3) || splitk > 1)) return (int)hipErrorInvalidValue;
     if (splitk < 1) splitk = 1;
@@ -1873,8 +1906,8 @@ int gemm_h16(const uint16_t* A, const uint16_t* B, void* C, int c_f32, int M, in
     const bool glds = (K % BK == 0) && M >= 8 && N >= 8;
     // large problems: 3-stage LDS-DMA pipeline (256x128 tiles)
     const bool pipe = glds && M >= 256 && N >= 128;
-    const bool short_tiles = tile_frags == 13;
-    if (short_tiles && (transA || transB || splitk != 1 || beta != 0.f || (N & 7) || (ldc & 7) || (ldaux & 7) || !pipe || N < 256))
+    // short tiles: as the row map, but with the CLAMPED split
+    if (o.tile_frags == 13 && (transA || transB || !pp_takes(M, N, K) || !pp_staged_ok(N, ldc, ldaux, splitk, beta)))
         return (int)hipErrorInvalidValue;                       // (an error, not a fallback: the column-sum layout depends on h)
     // split-K: per-split slabs in the workspace + a reduction kernel (pipelined path), else fp32 atomics into C
     const bool slabs = splitk > 1 && pipe && (transA || transB) && splitk_ws && ldc == N && (((long)M * N) & 3) == 0 &&
@@ -1884,27 +1917,17 @@ int gemm_h16(const uint16_t* A, const uint16_t* B, void* C, int c_f32, int M, in
                            (float*)C, (long)M, N, ldc, beta);
         EDITOR_LAUNCH_CHECK();
     }
-    GemmB16Args g{(const bf16_t*)A, (const bf16_t*)B, slabs ? (void*)splitk_ws : C, M, N, K, lda, ldb, ldc, alpha,
-                  slabs ? 0.f : beta, bias, rowscale, splitk, (M + BM - 1) / BM, (N + BN - 1) / BN, epilogue, aux, ldaux,
-                  slabs ? 1 : 0,
-                  m_live, transA ? 1 : 0, 0, want_colsum ? splitk_ws : nullptr, nullptr, force_pp ? 1 : 0, aux_grad ? 1 : 0,
-                  tile_frags, nullptr, nullptr, nullptr, 0, prefer_pipe ? 1 : 0, stagger, 0, rowmap};
-    if (rowmap) g.force_pp = 1;
+    GemmB16Args g = gemm_args(A, B, slabs ? (void*)splitk_ws : C, M, N, K, lda, ldb, ldc, alpha);
+    g.beta = slabs ? 0.f : beta; g.bias = bias; g.rowscale = rowscale; g.splitk = splitk; g.slabs = slabs;
+    g.tiles_m = (M + BM - 1) / BM; g.tiles_n = (N + BN - 1) / BN;
+    g.epilogue = epilogue; g.aux = aux; g.ldaux = ldaux; g.aux_grad = o.aux_grad; g.colsum = o.colsum ? splitk_ws : nullptr;
+    g.m_live = m_live; g.live_is_k = transA ? 1 : 0; g.rowmap = rowmap;
+    g.force_pp = o.force_pp || rowmap; g.tile_frags = o.tile_frags; g.stagger = o.stagger;      // (a row map forces it)
+    g.prefer_pipe = o.pipe128 && !o.colsum && !o.force_pp && o.tile_frags == 0;
     if (m_live && (!pipe || (splitk > 1 && !slabs))) return (int)hipErrorInvalidValue;   // live-row form: pipelined path only
-    const int sel = (transA ? 0 : 4) | (transB ? 0 : 2) | (c_f32 ? 1 : 0);
-    int rc;
-    if (pipe) {
-        switch (sel) {
-            case 7: rc = launch_pipe<F16, true, true, true>(g, stream); break;
-            case 6: rc = launch_pipe<F16, true, true, false>(g, stream); break;
-            case 5: rc = launch_pipe<F16, true, false, true>(g, stream); break;
-            case 4: rc = launch_pipe<F16, true, false, false>(g, stream); break;
-            case 3: rc = launch_pipe<F16, false, true, true>(g, stream); break;
-            case 2: rc = launch_pipe<F16, false, true, false>(g, stream); break;
-            case 1: rc = launch_pipe<F16, false, false, true>(g, stream); break;
-            default: rc = launch_pipe<F16, false, false, false>(g, stream); break;
-        }
-        if (rc) return rc;
+    return with_layout(!transA, !transB, c_f32 != 0, [&](auto ak, auto bk, auto cf) {    // (not transposed = k-major)
+        if (!pipe) return glds ? launch<F16, ak, bk, cf, true>(g, stream) : launch<F16, ak, bk, cf, false>(g, stream);
+        if (int rc = launch_pipe<F16, ak, bk, cf>(g, stream)) return rc;
         if (slabs) {
             const long n4 = (long)M * N / 4;
             long blocks = (n4 + 255) / 256;
@@ -1914,19 +1937,7 @@ int gemm_h16(const uint16_t* A, const uint16_t* B, void* C, int c_f32, int M, in
             EDITOR_LAUNCH_CHECK();
         }
         return 0;
-    }
-#define GEMM_CASE(n, a, b, c) case n: return glds ? launch<F16, a, b, c, true>(g, stream) : launch<F16, a, b, c, false>(g, stream)
-    switch (sel) {
-        GEMM_CASE(7, true, true, true);
-        GEMM_CASE(6, true, true, false);
-        GEMM_CASE(5, true, false, true);
-        GEMM_CASE(4, true, false, false);
-        GEMM_CASE(3, false, true, true);
-        GEMM_CASE(2, false, true, false);
-        GEMM_CASE(1, false, false, true);
-        default: return glds ? launch<F16, false, false, false, true>(g, stream) : launch<F16, false, false, false, false>(g, stream);
-    }
-#undef GEMM_CASE
+    });
 }
 
 // Forward product of the split-precision mode: C = alpha * (A_hi + A_lo)(B_hi + B_lo)^T (+bias) (*rowscale) (+aux residual /
@@ -1941,22 +1952,23 @@ int gemm_f16x2(const uint16_t* A_hi, const uint16_t* A_lo, const uint16_t* B_hi,
     const uintptr_t al = reinterpret_cast<uintptr_t>(A_hi) | reinterpret_cast<uintptr_t>(A_lo) | reinterpret_cast<uintptr_t>(B_hi) |
                          reinterpret_cast<uintptr_t>(B_lo) | reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(C_lo);
     if (al & 15) return (int)hipErrorInvalidValue;
-    const int tile_frags = (epilogue >> 12) & 15;
-    if (tile_frags != 0 && tile_frags != 13) return (int)hipErrorInvalidValue;
-    const bool aux_grad = (epilogue & EDITOR_EPI_AUX_GRAD) != 0;
-    epilogue &= ~(EDITOR_EPI_FORCE_PP | EDITOR_EPI_AUX_GRAD | 0xF000);
+    const EpiOptions o = decode_epilogue(epilogue);              // accepted: tile rows, AUX_GRAD, FORCE_PP
+    if (o.colsum || o.pipe128 || o.stagger) return (int)hipErrorInvalidValue;                  // not accepted here
+    if (o.tile_frags != 0 && o.tile_frags != 13) return (int)hipErrorInvalidValue;
     if (epilogue != EDITOR_EPI_NONE && epilogue != EDITOR_EPI_RESIDUAL && epilogue != EDITOR_EPI_GELU) return (int)hipErrorInvalidValue;
     if (epilogue != EDITOR_EPI_NONE && !aux && epilogue != EDITOR_EPI_GELU) return (int)hipErrorInvalidValue;   // (GELU, aux NULL: no-grad forward)
-    if (epilogue == EDITOR_EPI_GELU && (c_f32 || !aux_grad)) return (int)hipErrorInvalidValue;   // aux = gelu'(x) for the backward
+    if (epilogue == EDITOR_EPI_GELU && (c_f32 || !o.aux_grad)) return (int)hipErrorInvalidValue;   // aux = gelu'(x) for the backward
     if (epilogue == EDITOR_EPI_RESIDUAL && !c_f32) return (int)hipErrorInvalidValue;
-    if (rowmap && (epilogue != EDITOR_EPI_RESIDUAL || M < 256 || N < 256)) return (int)hipErrorInvalidValue;   // (see GemmB16Args::rowmap)
-    GemmB16Args g{(const bf16_t*)A_hi, (const bf16_t*)B_hi, C, M, N, K, lda, ldb, ldc, alpha, 0.f, bias, rowscale, 1, 0, 0,
-                  epilogue, aux, ldaux, 0, m_live, 0, 1, nullptr, nullptr, 1, 1, tile_frags,
-                  (const bf16_t*)A_lo, (const bf16_t*)B_lo, C_lo};
-    g.rowmap = rowmap;
-    if (tile_frags == 13)
-        return c_f32 ? launch_pp_t<true, true, true, true, 7, 6, true>(g, stream) : launch_pp_t<true, true, true, false, 7, 6, true>(g, stream);
-    return c_f32 ? launch_pp_t<true, true, true, true, 8, 8, true>(g, stream) : launch_pp_t<true, true, true, false, 8, 8, true>(g, stream);
+    // row map: as in gemm_h16 (the first check is the staged epilogue's, for every call)
+    if (rowmap && (epilogue != EDITOR_EPI_RESIDUAL || !pp_takes(M, N, K))) return (int)hipErrorInvalidValue;
+    GemmB16Args g = gemm_args(A_hi, B_hi, C, M, N, K, lda, ldb, ldc, alpha);
+    g.A_lo = (const bf16_t*)A_lo; g.B_lo = (const bf16_t*)B_lo; g.C_lo = C_lo; g.bias = bias; g.rowscale = rowscale; g.splitk = 1;
+    g.epilogue = epilogue; g.aux = aux; g.ldaux = ldaux; g.aux_grad = 1;      // (GELU without the option is refused)
+    g.m_live = m_live; g.rowmap = rowmap; g.pp_staged = 1; g.force_pp = 1; g.tile_frags = o.tile_frags;
+    return with_bool(c_f32 != 0, [&](auto cf) {
+        if (o.tile_frags == 13) return launch_pp_t<true, true, true, cf, 7, 6, true>(g, stream);
+        return launch_pp_t<true, true, true, cf, 8, 8, true>(g, stream);
+    });
 }
 
 // The weight gradients of one block in one launch (see gemm_bf16_pp_group_kernel).  Problem i: dW_i (N_i x K_i fp32, contiguous) =
@@ -1981,22 +1993,22 @@ int gemm_wgrad_group(int count, const uint16_t* const* dy, const uint16_t* const
         if ((reinterpret_cast<uintptr_t>(dy[i]) | reinterpret_cast<uintptr_t>(x[i]) | reinterpret_cast<uintptr_t>(dw[i])) & 15) return (int)hipErrorInvalidValue;
         slab[i] = ws + wsoff;
         // output (N_i, K_i); "A" = dy stored (Kred = M, N_i) row-k, "B" = x stored (Kred = M, K_i) row-k
-        GemmB16Args g{(const bf16_t*)dy[i], (const bf16_t*)x[i], (void*)slab[i], N[i], K[i], M, (long)N[i], (long)K[i], (long)K[i],
-                      alpha, 0.f, nullptr, nullptr, splitk, N[i] / 256, K[i] / 256, EDITOR_EPI_NONE, nullptr, (long)K[i], 1,
-                      m_live_each ? m_live_each[i] : m_live, 1, 1, nullptr, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, 1};
+        GemmB16Args g = gemm_args(dy[i], x[i], slab[i], N[i], K[i], M, N[i], K[i], K[i], alpha);
+        g.splitk = splitk; g.slabs = 1; g.tiles_m = N[i] / 256; g.tiles_n = K[i] / 256; g.ldaux = K[i];
+        g.m_live = m_live_each ? m_live_each[i] : m_live; g.live_is_k = 1;
+        g.pp_staged = 1; g.force_pp = 1; g.linear_ids = 1;
         ga.p[i] = g;
         ga.start[i] = tiles;
         tiles += g.tiles_m * g.tiles_n;
         wsoff += (long)splitk * N[i] * K[i];
     }
     ga.start[count] = tiles;
-    constexpr int LDS = 256 * (256 * 2 + 16) + (int)kLutBytes;
     if (ln) {
-        if (int e = ensure_lds<gemm_bf16_pp_group_ln_kernel<F16>>(LDS)) return e;
-        hipLaunchKernelGGL(gemm_bf16_pp_group_ln_kernel<F16>, dim3(ln->nmem + tiles * splitk), dim3(512), LDS, stream, ga, *ln);
+        if (int e = ensure_lds<gemm_bf16_pp_group_ln_kernel<F16>>(kPpLdsBytes)) return e;
+        hipLaunchKernelGGL(gemm_bf16_pp_group_ln_kernel<F16>, dim3(ln->nmem + tiles * splitk), dim3(512), kPpLdsBytes, stream, ga, *ln);
     } else {
-        if (int e = ensure_lds<gemm_bf16_pp_group_kernel<F16>>(LDS)) return e;
-        hipLaunchKernelGGL(gemm_bf16_pp_group_kernel<F16>, dim3(tiles * splitk), dim3(512), LDS, stream, ga);
+        if (int e = ensure_lds<gemm_bf16_pp_group_kernel<F16>>(kPpLdsBytes)) return e;
+        hipLaunchKernelGGL(gemm_bf16_pp_group_kernel<F16>, dim3(tiles * splitk), dim3(512), kPpLdsBytes, stream, ga);
     }
     EDITOR_LAUNCH_CHECK();
     SlabJobs sj;
@@ -2023,11 +2035,11 @@ int gemm_fwd_group(int count, const uint16_t* const* A, const uint16_t* const* B
 {
     if (count < 1 || count > kMaxGroup || M < 256 || N < 256 || (N & 255) || K < BK || (K % BK)) return (int)hipErrorInvalidValue;
     if ((lda & 7) || (ldb & 7) || (ldc & 7) || (ldaux & 7)) return (int)hipErrorInvalidValue;
-    const bool aux_grad = (epilogue & EDITOR_EPI_AUX_GRAD) != 0;
-    epilogue &= ~(EDITOR_EPI_FORCE_PP | EDITOR_EPI_AUX_GRAD);
+    const EpiOptions o = decode_epilogue(epilogue);              // accepted: AUX_GRAD, FORCE_PP
+    if (o.colsum || o.pipe128 || o.tile_frags || o.stagger) return (int)hipErrorInvalidValue;  // not accepted here
     if (epilogue != EDITOR_EPI_NONE && epilogue != EDITOR_EPI_RESIDUAL && epilogue != EDITOR_EPI_GELU && epilogue != EDITOR_EPI_GELU_BWD)
         return (int)hipErrorInvalidValue;
-    if (aux_grad && epilogue != EDITOR_EPI_GELU && epilogue != EDITOR_EPI_GELU_BWD) return (int)hipErrorInvalidValue;
+    if (o.aux_grad && epilogue != EDITOR_EPI_GELU && epilogue != EDITOR_EPI_GELU_BWD) return (int)hipErrorInvalidValue;
     GemmGroupArgs ga;
     memset(&ga, 0, sizeof(ga));
     ga.n = count;
@@ -2038,34 +2050,30 @@ int gemm_fwd_group(int count, const uint16_t* const* A, const uint16_t* const* B
         if (epilogue != EDITOR_EPI_NONE && !ax && epilogue != EDITOR_EPI_GELU) return (int)hipErrorInvalidValue;
         if ((reinterpret_cast<uintptr_t>(A[i]) | reinterpret_cast<uintptr_t>(B[i]) | reinterpret_cast<uintptr_t>(C[i])) & 15)
             return (int)hipErrorInvalidValue;
-        GemmB16Args g{(const bf16_t*)A[i], (const bf16_t*)B[i], C[i], M, N, K, lda, ldb, ldc, alpha, 0.f, bias ? bias[i] : nullptr,
-                      rowscale ? rowscale[i] : nullptr, 1, tiles_m, tiles_n, epilogue, ax, ldaux, 0, m_live, 0, 1, nullptr, nullptr, 1,
-                      aux_grad ? 1 : 0, 0, nullptr, nullptr, nullptr, 0, 0};
+        GemmB16Args g = gemm_args(A[i], B[i], C[i], M, N, K, lda, ldb, ldc, alpha);
+        g.bias = bias ? bias[i] : nullptr; g.rowscale = rowscale ? rowscale[i] : nullptr;
+        g.epilogue = epilogue; g.aux = ax; g.ldaux = ldaux; g.aux_grad = o.aux_grad; g.m_live = m_live;
+        g.splitk = 1; g.tiles_m = tiles_m; g.tiles_n = tiles_n; g.pp_staged = 1; g.force_pp = 1;
         ga.p[i] = g;
         ga.start[i] = i * tiles_m * tiles_n;
     }
     ga.start[count] = count * tiles_m * tiles_n;
     for (int i = count + 1; i <= kMaxGroup; ++i) ga.start[i] = ga.start[count];
-    constexpr int LDS = 256 * (256 * 2 + 16) + (int)kLutBytes;
-    const dim3 grid(count * tiles_m * tiles_n);
-    if (c_f32) {
-        if (int e = ensure_lds<gemm_bf16_pp_fgroup_kernel<F16, true>>(LDS)) return e;
-        hipLaunchKernelGGL((gemm_bf16_pp_fgroup_kernel<F16, true>), grid, dim3(512), LDS, stream, ga);
-    } else {
-        if (int e = ensure_lds<gemm_bf16_pp_fgroup_kernel<F16, false>>(LDS)) return e;
-        hipLaunchKernelGGL((gemm_bf16_pp_fgroup_kernel<F16, false>), grid, dim3(512), LDS, stream, ga);
-    }
-    EDITOR_LAUNCH_CHECK();
-    return 0;
+    return with_bool(c_f32 != 0, [&](auto cf) {
+        if (int e = ensure_lds<gemm_bf16_pp_fgroup_kernel<F16, cf>>(kPpLdsBytes)) return e;
+        hipLaunchKernelGGL((gemm_bf16_pp_fgroup_kernel<F16, cf>), dim3(count * tiles_m * tiles_n), dim3(512), kPpLdsBytes, stream, ga);
+        EDITOR_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 extern "C" int editor_gemm_group(int dtype, int count, const uint16_t* const* A, const uint16_t* const* B, void* const* C, int c_f32,
     int M, int N, int K, long lda, long ldb, long ldc, float alpha, const float* const* bias, const float* const* rowscale,
     int epilogue, void* const* aux, long ldaux, const int* m_live, hipStream_t stream)
 {
-    if (dtype == 2) return gemm_fwd_group<true>(count, A, B, C, c_f32, M, N, K, lda, ldb, ldc, alpha, bias, rowscale, epilogue, aux, ldaux, m_live, stream);
-    if (dtype == 1) return gemm_fwd_group<false>(count, A, B, C, c_f32, M, N, K, lda, ldb, ldc, alpha, bias, rowscale, epilogue, aux, ldaux, m_live, stream);
-    return (int)hipErrorInvalidValue;
+    return with_h16(dtype, [&](auto f16) {
+        return gemm_fwd_group<f16>(count, A, B, C, c_f32, M, N, K, lda, ldb, ldc, alpha, bias, rowscale, epilogue, aux, ldaux, m_live, stream);
+    });
 }
 
 #ifdef EDITOR_DEBUG_TRACE
@@ -2119,10 +2127,9 @@ extern "C" int editor_probe_gemm_hetero_ln(const uint16_t* A, const uint16_t* B,
     GemmB16Args g{(const bf16_t*)A, (const bf16_t*)B, C, M, N, K, (long)K, (long)K, (long)N, 1.f, 0.f, bias, nullptr, 1, tiles_m, tiles_n,
                   EDITOR_EPI_NONE, nullptr, (long)N, 0, nullptr, 0, 1, nullptr, nullptr, 1, 0, 0, nullptr, nullptr, nullptr, 0, 0};
     LnRoleArgs ln{ln_dy, ln_x, gamma, mean, rstd, ln_M, 768, dx_in, dx_out, partials, 1.f, cast_out, nullptr, 1.f, cast_partials, nmem};
-    constexpr int LDS = 256 * (256 * 2 + 16) + (int)kLutBytes;
-    if (int e = ensure_lds<gemm_hetero_ln_probe_kernel<false>>(LDS)) return e;
+    if (int e = ensure_lds<gemm_hetero_ln_probe_kernel<false>>(kPpLdsBytes)) return e;
     const int grid = nmem + (with_tiles ? tiles_m * tiles_n : 0);
-    hipLaunchKernelGGL((gemm_hetero_ln_probe_kernel<false>), dim3(grid), dim3(512), LDS, stream, g, ln);
+    hipLaunchKernelGGL((gemm_hetero_ln_probe_kernel<false>), dim3(grid), dim3(512), kPpLdsBytes, stream, g, ln);
     EDITOR_LAUNCH_CHECK();
     return 0;
 }
@@ -2141,11 +2148,10 @@ extern "C" int editor_probe_gemm_hetero(const uint16_t* A, const uint16_t* B, vo
     h.g = g;
     h.s0 = reinterpret_cast<const float4_t*>(s0); h.s1 = reinterpret_cast<const float4_t*>(s1); h.d = reinterpret_cast<float4_t*>(d);
     h.n4 = n4; h.nmem = nmem;
-    constexpr int LDS = 256 * (256 * 2 + 16) + (int)kLutBytes;
     const int grid = nmem + (with_tiles ? tiles_m * tiles_n : 0);
     if (grid < 1) return (int)hipErrorInvalidValue;
-#define HETERO_CASE(Uv) case Uv: { if (int e = ensure_lds<gemm_hetero_probe_kernel<false, Uv>>(LDS)) return e;                 \
-        hipLaunchKernelGGL((gemm_hetero_probe_kernel<false, Uv>), dim3(grid), dim3(512), LDS, stream, h); break; }
+#define HETERO_CASE(Uv) case Uv: { if (int e = ensure_lds<gemm_hetero_probe_kernel<false, Uv>>(kPpLdsBytes)) return e;         \
+        hipLaunchKernelGGL((gemm_hetero_probe_kernel<false, Uv>), dim3(grid), dim3(512), kPpLdsBytes, stream, h); break; }
     switch (unroll) { HETERO_CASE(4) HETERO_CASE(8) HETERO_CASE(16) default: return (int)hipErrorInvalidValue; }
 #undef HETERO_CASE
     EDITOR_LAUNCH_CHECK();
@@ -2156,9 +2162,7 @@ extern "C" int editor_probe_gemm_hetero(const uint16_t* A, const uint16_t* B, vo
 extern "C" int editor_gemm_wgrad_group(int dtype, int count, const uint16_t* const* dy, const uint16_t* const* x, float* const* dw,
     const int* N, const int* K, int M, float alpha, int splitk, float* ws, const int* m_live, hipStream_t stream)
 {
-    if (dtype == 2) return gemm_wgrad_group<true>(count, dy, x, dw, N, K, M, alpha, splitk, ws, m_live, stream);
-    if (dtype == 1) return gemm_wgrad_group<false>(count, dy, x, dw, N, K, M, alpha, splitk, ws, m_live, stream);
-    return (int)hipErrorInvalidValue;
+    return with_h16(dtype, [&](auto f16) { return gemm_wgrad_group<f16>(count, dy, x, dw, N, K, M, alpha, splitk, ws, m_live, stream); });
 }
 
 // editor_gemm_wgrad_group with a live-row count PER PROBLEM (m_live: host array of `count` device scalars, NULL entries = all M rows):
@@ -2167,9 +2171,9 @@ extern "C" int editor_gemm_wgrad_group_live(int dtype, int count, const uint16_t
     const int* N, const int* K, int M, float alpha, int splitk, float* ws, const int* const* m_live, hipStream_t stream)
 {
     if (!m_live) return (int)hipErrorInvalidValue;
-    if (dtype == 2) return gemm_wgrad_group<true>(count, dy, x, dw, N, K, M, alpha, splitk, ws, nullptr, stream, nullptr, m_live);
-    if (dtype == 1) return gemm_wgrad_group<false>(count, dy, x, dw, N, K, M, alpha, splitk, ws, nullptr, stream, nullptr, m_live);
-    return (int)hipErrorInvalidValue;
+    return with_h16(dtype, [&](auto f16) {
+        return gemm_wgrad_group<f16>(count, dy, x, dw, N, K, M, alpha, splitk, ws, nullptr, stream, nullptr, m_live);
+    });
 }
 
 extern "C" int editor_gemm_wgrad_group_ln(int dtype, int count, const uint16_t* const* dy, const uint16_t* const* x, float* const* dw,
@@ -2186,9 +2190,7 @@ extern "C" int editor_gemm_wgrad_group_ln(int dtype, int count, const uint16_t* 
         return (int)hipErrorInvalidValue;
     LnRoleArgs ln{ln_dy, ln_x, gamma, mean, rstd, ln_M, D, dx_in, dx_out, partials, ln_dy_scale, cast_out, cast_rowscale, cast_scale,
                   cast_partials, nmem};
-    if (dtype == 2) return gemm_wgrad_group<true>(count, dy, x, dw, N, K, M, alpha, splitk, ws, nullptr, stream, &ln);
-    if (dtype == 1) return gemm_wgrad_group<false>(count, dy, x, dw, N, K, M, alpha, splitk, ws, nullptr, stream, &ln);
-    return (int)hipErrorInvalidValue;
+    return with_h16(dtype, [&](auto f16) { return gemm_wgrad_group<f16>(count, dy, x, dw, N, K, M, alpha, splitk, ws, nullptr, stream, &ln); });
 }
 
 extern "C" int editor_gemm_f16x2(const uint16_t* A_hi, const uint16_t* A_lo, const uint16_t* B_hi, const uint16_t* B_lo, void* C,
@@ -2232,9 +2234,8 @@ extern "C" int editor_gemm_h16_rows(int dtype, const uint16_t* A, const uint16_t
     const int* rowmap, hipStream_t stream)
 {
     if (!rowmap) return (int)hipErrorInvalidValue;
-    if (dtype == 2) return gemm_h16<true>(A, B, C, 1, M, N, K, lda, ldb, ldc, 0, 0, alpha, 0.f, bias, rowscale, 1, epilogue, aux, ldaux,
-                                          nullptr, m_live, stream, rowmap);
-    if (dtype == 1) return gemm_h16<false>(A, B, C, 1, M, N, K, lda, ldb, ldc, 0, 0, alpha, 0.f, bias, rowscale, 1, epilogue, aux, ldaux,
-                                           nullptr, m_live, stream, rowmap);
-    return (int)hipErrorInvalidValue;
+    return with_h16(dtype, [&](auto f16) {
+        return gemm_h16<f16>(A, B, C, 1, M, N, K, lda, ldb, ldc, 0, 0, alpha, 0.f, bias, rowscale, 1, epilogue, aux, ldaux, nullptr, m_live,
+                             stream, rowmap);
+    });
 }

@@ -2,6 +2,7 @@
 function allocates outputs with torch (device memory plumbing) and launches HIP kernels on the
 current stream.  Every function raises on CPU tensors - there is no fallback path."""
 import ctypes
+import functools
 import os
 
 import torch
@@ -465,6 +466,7 @@ def EPI_TILE_ROWS(h):
     return ((h // 16) & 15) << 12
 
 
+@functools.lru_cache(maxsize=None)                          # (pure; asked once per product of every step)
 def gemm_tile_rows(m, n, cus=256):
     """Tile height for a forward / dgrad product on the ping-pong kernel (k-major operands, staged epilogue): 208 when that
     does not add a round of `cus` workgroups, else 256.  The path's M = 49 536 rows x 768 columns: 582 full tiles = 2.27
@@ -482,6 +484,7 @@ def gemm_tile_rows(m, n, cus=256):
     return best
 
 
+@functools.lru_cache(maxsize=None)
 def gemm_tile_plan(m, n, cus=256):
     """-> (tile rows of the ping-pong kernel, prefer the 256x128 kernel?) for a forward / dgrad product with k-major operands.
     Rounds of `cus` workgroups x relative tile time: a 208-row tile costs 0.95 of a 256-row one (gemm_tile_rows); a 256x128 tile
@@ -496,12 +499,29 @@ def gemm_tile_plan(m, n, cus=256):
     return th, cost_pipe < 0.97 * cost_pp
 
 
+def _pp_big(m, n, k, min_n=512):    # shape of a "big ping-pong product" (gemm_bf16.hip: pp_big, pp_staged_ok); 256: a group fills the CUs
+    return m >= 2048 and n >= min_n and n % 8 == 0 and k % 64 == 0
+
+
+def gemm_flags(m, n, k, ldc, trans_a=0, trans_b=0, splitk=1, beta=0.0, live=False, live_dense=False, epilogue=0, needs_pp=0, pair=0):
+    """-> epilogue with the kernel-selection flags (tile rows or EPI_PIPE128) that ops.gemm / (pair) ops.gemm_split add on their own.
+    live: a live-row count; live_dense: ... over zero tail rows; needs_pp: colsum or rowmap wanted."""
+    epilogue = int(epilogue)
+    if not SHORT_TILES or (epilogue & 0xF000) or (live and not live_dense) or m < 2048 or n < 512:
+        return epilogue                                     # (an explicit EPI_TILE_ROWS stands)
+    if not pair:
+        if trans_a or trans_b or splitk != 1 or beta != 0.0 or ldc % 8 or not _pp_big(m, n, k):
+            return epilogue
+        if gemm_tile_plan(m, n)[1] and not (needs_pp or epilogue & EPI_FORCE_PP):
+            return epilogue | EPI_PIPE128
+    return epilogue | EPI_TILE_ROWS(gemm_tile_rows(m, n))
+
+
 def gemm_colsum_ok(m, n, k, c_dtype, trans_a, splitk, m_live, live_dense=False):
     """Can the 16-bit GEMM also deliver the column sums of its (16-bit) output?  (one-pass 256x256 epilogue only)
     live_dense: m_live counts the live prefix of stochastic-depth-compacted rows whose tail rows are ZERO (droppath_plan) - the
     skipped tiles zero their partial rows; the compacted HMA head's live rows (unwritten tails) do not qualify."""
-    return (c_dtype in HALF_DTYPES and not trans_a and splitk == 1 and (m_live is None or live_dense) and m >= 2048 and n >= 512
-            and n % 8 == 0 and k % 64 == 0)
+    return c_dtype in HALF_DTYPES and not trans_a and splitk == 1 and (m_live is None or live_dense) and _pp_big(m, n, k)
 
 
 def gemm(a, b, c, m, n, k, lda, ldb, ldc, trans_a=0, trans_b=0, alpha=1.0, beta=0.0, bias=None, rowscale=None,
@@ -545,35 +565,29 @@ def gemm(a, b, c, m, n, k, lda, ldb, ldc, trans_a=0, trans_b=0, alpha=1.0, beta=
             gemm(a, b, c, m, n, k - k0, lda, ldb, ldc, 1, 1, alpha=alpha, beta=1.0, rowscale=rowscale, splitk=1,
                  a_off=a_off + k0 * lda, b_off=b_off + k0 * ldb, c_off=c_off)
             return
-        th = ((int(epilogue) >> 12) & 15) * 16 or 256            # explicit EPI_TILE_ROWS, else the shape heuristic
-        if (SHORT_TILES and not trans_a and not trans_b and splitk == 1 and beta == 0.0 and (m_live is None or live_dense) and m >= 2048
-                and n >= 512 and n % 8 == 0 and ldc % 8 == 0 and k % 64 == 0 and not (int(epilogue) & 0xF000)):
-            th, narrow = gemm_tile_plan(m, n)
-            if narrow and colsum is None and rowmap is None and not (int(epilogue) & EPI_FORCE_PP):     # (a row map needs the ping-pong kernel)
-                th, epilogue = 256, int(epilogue) | EPI_PIPE128
-            elif th != 256:
-                epilogue = int(epilogue) | EPI_TILE_ROWS(th)
+        epilogue = gemm_flags(m, n, k, ldc, trans_a, trans_b, splitk, beta, m_live is not None, live_dense, epilogue,
+                              colsum is not None or rowmap is not None)
         if colsum is not None:
             # colsum (n) fp32 <- column sums of the rounded output (bias gradient of the layer this gradient feeds):
             # per-tile-row partials from the GEMM epilogue, folded in a fixed order
             assert gemm_colsum_ok(m, n, k, c.dtype, trans_a, splitk, m_live, live_dense) and ldc == n and rowmap is None
-            tiles_m = (m + th - 1) // th
+            tiles_m = -(-m // (((epilogue >> 12) & 15) * 16 or 256))
             part, queued = _parts_buf(rq, a.device, tiles_m * n)
             call(entry, _ptr(a, a_off), _ptr(b, b_off), _ptr(c, c_off), 0, m, n, k, lda, ldb, ldc,
-                 int(trans_a), int(trans_b), float(alpha), float(beta), bias, rowscale, 1, int(epilogue) | EPI_COLSUM, aux,
+                 int(trans_a), int(trans_b), float(alpha), float(beta), bias, rowscale, 1, epilogue | EPI_COLSUM, aux,
                  n, part, m_live)
             _fold(rq, queued, part, tiles_m, n, colsum, colsum_scale)
             return
         if rowmap is not None:
             # compacted rows scattered back by the fp32 residual epilogue (stochastic-depth skipping: editor_gemm_h16_rows)
             assert c.dtype == torch.float32 and not trans_a and not trans_b and splitk == 1 and beta == 0.0
-            assert a_off == b_off == c_off == 0 and (int(epilogue) & 0xFF) == EPI_RESIDUAL
+            assert a_off == b_off == c_off == 0 and (epilogue & 0xFF) == EPI_RESIDUAL
             call("editor_gemm_h16_rows", _DT_CODE[a.dtype], a, b, c, m, n, k, lda, ldb, ldc, float(alpha), bias, rowscale,
-                 int(epilogue), aux, n, m_live, rowmap)
+                 epilogue, aux, n, m_live, rowmap)
             return
         call(entry, _ptr(a, a_off), _ptr(b, b_off), _ptr(c, c_off), 1 if c.dtype == torch.float32 else 0,
              m, n, k, lda, ldb, ldc, int(trans_a), int(trans_b), float(alpha), float(beta), bias, rowscale, int(splitk),
-             int(epilogue), aux, n, workspace(a.device, int(splitk) * m * n) if splitk > 1 else None, m_live)
+             epilogue, aux, n, workspace(a.device, int(splitk) * m * n) if splitk > 1 else None, m_live)
     else:
         raise TypeError(a.dtype)
 
@@ -649,17 +663,14 @@ def gemm_split(a, b, c, c_lo, m, n, k, alpha=1.0, bias=None, rowscale=None, epil
                rowmap=None):
     """c (fp32, c_lo None) or (c, c_lo) half pair = alpha * (a_hi + a_lo)(b_hi + b_lo)^T (+bias) (*rowscale) (+epilogue);
     a = (hi, lo) (M,K), b = (hi, lo) (N,K), all contiguous.  live_dense / rowmap: as ops.gemm (stochastic-depth-compacted rows)."""
-    if SHORT_TILES and m >= 2048 and n >= 512 and (m_live is None or live_dense) and not (int(epilogue) & 0xF000):
-        th = gemm_tile_rows(m, n)
-        if th != 256:
-            epilogue = int(epilogue) | EPI_TILE_ROWS(th)
+    epilogue = gemm_flags(m, n, k, n, live=m_live is not None, live_dense=live_dense, epilogue=epilogue, pair=True)
     if rowmap is not None:
-        assert c.dtype == torch.float32 and c_lo is None and (int(epilogue) & 0xFF) == EPI_RESIDUAL
-        call("editor_gemm_f16x2_rows", a[0], a[1], b[0], b[1], c, m, n, k, k, k, n, float(alpha), bias, rowscale, int(epilogue), aux,
+        assert c.dtype == torch.float32 and c_lo is None and (epilogue & 0xFF) == EPI_RESIDUAL
+        call("editor_gemm_f16x2_rows", a[0], a[1], b[0], b[1], c, m, n, k, k, k, n, float(alpha), bias, rowscale, epilogue, aux,
              n, m_live, rowmap)
         return
     call("editor_gemm_f16x2", a[0], a[1], b[0], b[1], c, c_lo, 1 if c.dtype == torch.float32 else 0, m, n, k, k, k, n,
-         float(alpha), bias, rowscale, int(epilogue), aux, n, m_live)
+         float(alpha), bias, rowscale, epilogue, aux, n, m_live)
 
 
 def attention_fwd_split(qkv, b, t, heads, hd, mask=None, probs=None, cu=None, scale=None):
@@ -716,7 +727,7 @@ def gemm_group_ok(reqs):
         return False
     a0, kw0 = reqs[0]
     (a, b, c, m, n, k, lda, ldb, ldc), ta, tb = a0[:9], a0[9] if len(a0) > 9 else 0, a0[10] if len(a0) > 10 else 0
-    if a.dtype not in HALF_DTYPES or ta or tb or m < 2048 or n < 256 or n % 256 or k % 64 or kw0.get("m_live") is None:
+    if a.dtype not in HALF_DTYPES or ta or tb or not _pp_big(m, n, k, min_n=256) or n % 256 or kw0.get("m_live") is None:
         return False
     if lda != k or ldb != k or ldc != n:
         return False
@@ -755,27 +766,29 @@ def gemm_wgrad_group(jobs, m, alpha=1.0, m_live=None):
     """jobs: list of (dy (m, n_i), x (m, k_i), dw (n_i, k_i) fp32[, live_i]) of ONE block -> one launch (editor_gemm_wgrad_group).
     live_i (optional 4th entry): device scalar, live token rows of THAT problem (rows beyond are zero) - a block whose MLP branch
     ran on stochastic-depth-compacted rows next to its dense attention branch (editor_gemm_wgrad_group_live)."""
-    cnt = len(jobs)
     lives = [j[3] if len(j) > 3 else None for j in jobs]
-    jobs = [j[:3] for j in jobs]
+    head = _wgrad_group_args([j[:3] for j in jobs], m, alpha)
+    if any(l_ is not None for l_ in lives):
+        assert m_live is None
+        la = (ctypes.c_void_p * len(jobs))(*[None if l_ is None else l_.data_ptr() for l_ in lives])
+        return call("editor_gemm_wgrad_group_live", *head, la)
+    call("editor_gemm_wgrad_group", *head, m_live)
+
+
+def _wgrad_group_args(jobs, m, alpha):
+    """-> what every grouped weight-gradient entry starts with (dtype code .. slab workspace) for contiguous (dy, x, dw) jobs."""
+    cnt = len(jobs)
     dt = _DT_CODE[jobs[0][0].dtype]
     ns = [j[0].shape[1] for j in jobs]
     ks = [j[1].shape[1] for j in jobs]
     tiles = sum((n // 256) * (k // 256) for n, k in zip(ns, ks))
     sk = wgrad_group_split(tiles, m // 64)
     ws = workspace(jobs[0][0].device, sk * sum(n * k for n, k in zip(ns, ks)))
-    arr = lambda ts: (ctypes.c_void_p * cnt)(*[t.data_ptr() for t in ts])
-    ia = lambda v: (ctypes.c_int * cnt)(*v)
+    assert all(len(j) == 3 for j in jobs)                    # (live counts: gemm_wgrad_group alone, which strips them)
     for dy, x, dw in jobs:
         assert dy.is_contiguous() and x.is_contiguous() and dw.is_contiguous() and dy.shape[0] == m == x.shape[0]
-    if any(l_ is not None for l_ in lives):
-        assert m_live is None
-        la = (ctypes.c_void_p * cnt)(*[None if l_ is None else l_.data_ptr() for l_ in lives])
-        call("editor_gemm_wgrad_group_live", dt, cnt, arr([j[0] for j in jobs]), arr([j[1] for j in jobs]), arr([j[2] for j in jobs]),
-             ia(ns), ia(ks), m, float(alpha), sk, ws, la)
-        return
-    call("editor_gemm_wgrad_group", dt, cnt, arr([j[0] for j in jobs]), arr([j[1] for j in jobs]), arr([j[2] for j in jobs]),
-         ia(ns), ia(ks), m, float(alpha), sk, ws, m_live)
+    ptrs = [(ctypes.c_void_p * cnt)(*[j[i].data_ptr() for j in jobs]) for i in range(3)]
+    return (dt, cnt, *ptrs, (ctypes.c_int * cnt)(*ns), (ctypes.c_int * cnt)(*ks), m, float(alpha), sk, ws)
 
 
 WGRAD_LN_CUS = int(os.environ.get("EDITOR_WGRAD_LN_CUS", "64"))      # workgroups (= CUs) of the memory role, a multiple of 8
@@ -786,19 +799,8 @@ def gemm_wgrad_group_ln(jobs, m, alpha, dy, x2d, gamma, mean, rstd, dx_in, rowsc
     """gemm_wgrad_group(jobs, m, alpha) AND layernorm_bwd_cast(dy, x2d, gamma, mean, rstd, dx_in, rowscale, scale, dy_scale, ...) in ONE
     launch: the LayerNorm backward as a memory-bound role on `nmem` CUs beside the weight-gradient tiles on the others
     (include/editor_hip.h: editor_gemm_wgrad_group_ln).  -> dx, dgamma, dbeta, dx16, colsum(dx16) / scale (None unless want_colsum)."""
-    cnt = len(jobs)
     nmem = int(nmem or WGRAD_LN_CUS)
-    dt = _DT_CODE[jobs[0][0].dtype]
-    ns = [j[0].shape[1] for j in jobs]
-    ks = [j[1].shape[1] for j in jobs]
-    tiles = sum((n // 256) * (k // 256) for n, k in zip(ns, ks))
-    sk = wgrad_group_split(tiles, m // 64)
-    ws = workspace(jobs[0][0].device, sk * sum(n * k for n, k in zip(ns, ks)))
-    arr = lambda ts: (ctypes.c_void_p * cnt)(*[t.data_ptr() for t in ts])
-    ia = lambda v: (ctypes.c_int * cnt)(*v)
-    assert all(len(j) == 3 for j in jobs)                    # (no per-problem live counts in the role form)
-    for jdy, jx, jdw in jobs:
-        assert jdy.is_contiguous() and jx.is_contiguous() and jdw.is_contiguous() and jdy.shape[0] == m == jx.shape[0]
+    head = _wgrad_group_args(jobs, m, alpha)                 # (no per-problem live counts in the role form)
     rows, d = x2d.shape
     assert dy.dtype == jobs[0][0].dtype and dy.shape == x2d.shape and d in (768, 1024)
     dev = x2d.device
@@ -810,10 +812,8 @@ def gemm_wgrad_group_ln(jobs, m, alpha, dy, x2d, gamma, mean, rstd, dx_in, rowsc
         cs = cs_out if cs_out is not None else torch.empty(d, dtype=torch.float32, device=dev)
     parts, queued = _parts_buf(rq, dev, nmem * 3 * d, fresh=True)
     cparts = parts[nmem * 2 * d:]
-    call("editor_gemm_wgrad_group_ln", dt, cnt, arr([j[0] for j in jobs]), arr([j[1] for j in jobs]), arr([j[2] for j in jobs]),
-         ia(ns), ia(ks), m, float(alpha), sk, ws,
-         dy, float(dy_scale), x2d, gamma, mean, rstd, rows, d, dx_in, dx, parts, dx16, rowscale, float(scale),
-         cparts if want_colsum else None, nmem)
+    call("editor_gemm_wgrad_group_ln", *head, dy, float(dy_scale), x2d, gamma, mean, rstd, rows, d, dx_in, dx, parts, dx16, rowscale,
+         float(scale), cparts if want_colsum else None, nmem)
     _fold(rq, queued, parts, nmem, 2 * d, dgb)
     if want_colsum:
         _fold(rq, queued, cparts, nmem, d, cs, 1.0 / float(scale))

@@ -35,21 +35,21 @@ typedef struct ihipStream_t* editor_stream_t;   /* == hipStream_t */
 #define EDITOR_EPI_GELU 2     /* aux = v ; C = gelu(v)   aux: pre-activation in the activation dtype (Mlp.fc1 -> act, :140-141);
                                * 16-bit kernels: aux may be NULL (a no-grad forward saves nothing: one output instead of two) */
 #define EDITOR_EPI_GELU_BWD 3 /* C = v * gelu'(aux)      aux: saved pre-activation (backward of the above) */
-#define EDITOR_EPI_COLSUM 0x100 /* OR-able (editor_gemm_bf16, bf16 C, M >= 2048, N >= 512, A k-major, splitk 1): also write
-                                 * the column sums of every 256-row tile of the ROUNDED C to splitk_ws[(M+255)/256][N] - the bias
-                                 * gradient of the layer this gradient feeds, folded by editor_reduce_rows */
+#define EDITOR_EPI_COLSUM 0x100 /* OR-able (editor_gemm_bf16 / _f16, 16-bit C, no residual, M >= 2048, N >= 512, A k-major, splitk 1, beta 0,
+                                 * K % 64 == 0, N, ldc, ldaux % 8 == 0): also write the column sums of every tile row of the ROUNDED C to
+                                 * splitk_ws[ceil(M / tile rows)][N] - the bias gradient of the layer this gradient feeds (editor_reduce_rows) */
 #define EDITOR_EPI_AUX_GRAD 0x400 /* OR-able with EDITOR_EPI_GELU / _GELU_BWD (16-bit kernels): aux holds gelu'(pre-activation) instead
                                    * of the pre-activation - the forward saves the derivative (the only thing the backward needs of it), so
                                    * the dgrad epilogue is one multiply instead of an erfc + exponential per element */
-#define EDITOR_EPI_FORCE_PP 0x200 /* OR-able: run the 256x256 ping-pong kernel whatever the shape heuristic says (N >= 256,
-                                   * whole 64-deep K-tiles); tests use it to reach that kernel's edge cases */
+#define EDITOR_EPI_FORCE_PP 0x200 /* OR-able: run the 256x256 ping-pong kernel whatever the shape heuristic says (M >= 256,
+                                   * N >= 256, whole 64-deep K-tiles; ignored below that); tests use it to reach that kernel's edge cases */
 #define EDITOR_EPI_PIPE128 0x800 /* OR-able: prefer the 256x128 three-stage kernel over the 256x256 ping-pong kernel (few token rows:
                                   * twice the tiles fill more of the 256 CUs; the caller's tile-count heuristic decides,
-                                  * editor_amd.ops.gemm).  Ignored with EDITOR_EPI_COLSUM / _FORCE_PP / _TILE_ROWS. */
+                                  * editor_amd.ops.gemm_flags).  Ignored with EDITOR_EPI_COLSUM / _FORCE_PP / _TILE_ROWS; refused by _f16x2, _group. */
 #define EDITOR_EPI_STAGGER(c) (((c) & 63) << 17) /* OR-able (256x256 ping-pong kernel, more than 256 tiles; ignored otherwise): the
                                   * first round's workgroups start spread over c * 2048 shader cycles, so that the CUs leave
                                   * lockstep and one CU's HBM-bound epilogue runs beside the others' K loops.  Same results bit
-                                  * for bit.  The caller picks c ~ one tile period (editor_amd.ops.gemm_stagger). */
+                                  * for bit.  The caller picks c ~ one tile period.  editor_gemm_bf16 / _f16 only. */
 #define EDITOR_EPI_TILE_ROWS(h) ((((h) / 16) & 15) << 12) /* OR-able, h = 208 | 256 (ping-pong kernel, both operands k-major,
                                    * split-K 1, beta 0, M >= 256, N >= 256 and N, ldc, ldaux multiples of 8, K % 64 == 0): rows per
                                    * output tile.  M = 49 536 token rows x 768 columns are 582 full

@@ -1,7 +1,7 @@
 """How much does a ROUND of tiles cost beyond the tile itself?  t(r rounds) for r = 1 .. 4 (M = r x 21 760 rows, N = 768 or 2 304,
 K = 768, 256-row tiles, call by call with idle gaps): the slope is the time per round, to be held against the in-kernel tile time of
 tools/gemm_tile_ends.py - the difference is what the hardware needs to retire 256 workgroups and start the next 256.
-    python tools/gemm_round_gap.py [--persist]      (--persist: EDITOR_EPI_PERSIST, one workgroup per CU walking its tiles)
+    python tools/gemm_round_gap.py
 """
 import os
 import sys
@@ -18,8 +18,6 @@ def main():
     g = torch.Generator(device=dev).manual_seed(0)
     gap = lambda: torch.cuda._sleep(400000)
     flags = [("plain launch", ops.EPI_FORCE_PP)]
-    if hasattr(ops, "EPI_PERSIST"):
-        flags.append(("persistent", ops.EPI_FORCE_PP | ops.EPI_PERSIST))
     for n, k in ((768, 768), (2304, 768), (768, 3072)):
         per_round_rows = 256 * (255 // (n // 256))
         for name, fl in flags:

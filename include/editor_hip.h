@@ -464,6 +464,21 @@ int editor_rank_sort(const float* dist, int Q, int G, int P, unsigned long long*
 int editor_rank_metrics(const int* order, const long* q_pids, const long* g_pids, const long* q_aux, const long* g_aux,
                         int Q, int G, int max_rank, double* ap, int* first_pos, double* totals, int* cmc_counts,
                         editor_stream_t stream);
+/* Per-query rank lists (the `re.txt` lists of utils/metrics.py:92-99) without ranking the whole row: a filtered running top-K
+ * over one block of Gc gallery columns of a distance matrix, dist (Q, Gc) with row stride ldd, whose first column is gallery
+ * entry g0.  Keys are editor_rank_sort's (orderable distance << 32 | g0 + column), so exactly tied distances rank by gallery
+ * index and the finished list equals the first K kept entries of editor_rank_sort's order.  q_pids (Q), g_pids, q_aux, g_aux
+ * (indexed by GLOBAL gallery index): an entry with the query's pid AND aux id never enters the list; all four NULL = no filter,
+ * anything in between is refused.  list (Q, K): the caller's running lists, ascending, all-ones in the empty slots - fill it
+ * with all-ones before the first block, then feed the blocks one after another in any order.  slices >= 1 workgroups share each
+ * row (for Q far below the CU count); slices > 1 needs work = Q * slices * K keys of scratch.
+ * Limits (non-zero return): 1 <= K <= 1024, g0 + Gc <= 2^31 - 1, slices <= 1024. */
+int editor_rank_topk(const float* dist, long ldd, int Q, int Gc, long g0, const long* q_pids, const long* g_pids,
+                     const long* q_aux, const long* g_aux, int K, unsigned long long* list, unsigned long long* work,
+                     int slices, editor_stream_t stream);
+/* list (Q, K) -> index (Q, K) int32 gallery indices and dist (Q, K) fp32, the distance recovered bit-exactly from the key's high
+ * word; an empty slot gives index -1 and distance +inf. */
+int editor_rank_topk_finish(const unsigned long long* list, int Q, int K, int* index, float* dist, editor_stream_t stream);
 
 /* k-reciprocal re-ranking (utils/metrics.py:275-278 -> utils/reranking.py:30-101), dense over ALL N = Q + G images; the caller
  * (editor_amd.metrics.re_ranking) strings the stages together: editor_distmat_f32(feat, feat) -> _normalise -> editor_rank_sort(od)

@@ -446,6 +446,18 @@ int editor_triplet_loss_fwd(const float* feat, long ldf, const long* label, int 
 int editor_normalize_rows_fwd(const float* x, long ldx, int B, int D, float* y, float* norm, editor_stream_t stream);
 int editor_normalize_rows_bwd(const float* g, const float* y, const float* norm, int B, int D, float* dx, editor_stream_t stream);
 
+/* engine/processor.py:97-105 without its host reads: one training iteration's meters, device-resident, hipGraph-replay safe.
+ * score (B,C) fp32, row stride lds >= C; target (B) int64; loss: one fp32.
+ * correct = #{ b : argmax_c score[b,:] == target[b] }; argmax as torch.max(1)[1]: the FIRST index of the maximum,
+ *   and a NaN counts as the maximum (first NaN of the row).  A target outside [0,C) simply never matches.
+ * state (double[4]):  [0] += (double)loss[0] * B   [1] += B   [2] += (double)((float)correct / (float)B)   [3] += 1
+ * last  (int[2]):     last[0] = correct, last[1] = B
+ * One launch of ONE workgroup (a wave per row, 16 rows at a time): no scratch, no counter to reset, every sum in a fixed order, so
+ * the state is bit-reproducible.  Nothing past score + (B-1)*lds + C is read.
+ * B < 1, C < 1, lds < C or a NULL pointer: the invalid-value return (1), nothing launched. */
+int editor_train_meter(const float* score, long lds, const long* target, const float* loss, int B, int C, double* state, int* last,
+                       editor_stream_t stream);
+
 /* ---- retrieval evaluation (utils/metrics.py consumes the hot path's eval-mode features) ------ */
 
 /* F.normalize(x, p=2, dim=1): y = x / max(||x||, eps) (utils/metrics.py:259-261). */

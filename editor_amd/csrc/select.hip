@@ -171,7 +171,8 @@ __global__ __launch_bounds__(256) void freq_counts_kernel(
 // (q = RN(x * RN(1/3)); r = fma(-q, 3, x) exact; RN(q + r * RN(1/3)) = RN(x / 3): Markstein) with the IEEE sequence kept for
 // the inputs it does not cover (denormals, infinities: a wave-uniform, never-taken branch on image data).  ~1 600 instructions
 // per 16 pixels: 3.7x fewer per pixel, same arithmetic per element (same haar_fwd / haar_inv expressions, same summation
-// orders) - bit-identical counts (tests/test_gpu_select.py against the reference's goldens and against the kernel above).
+// orders) - bit-identical counts (tests/test_gpu_select.py against the reference's goldens;
+// tests/test_gpu_select_edges.py::test_frequency_4x4_and_2x2_forms_count_alike against the kernel above, on the same pixels).
 // Built for 2, 3 and 4 modalities.  Two (forward_two_modalities, RGB + NIR): the mean is an exact halving of (Ylx + Yly), summed in
 // that order as Frequency.py:76-79 does, so the rare-input branch never fires for it.
 template <int XM> __device__ __forceinline__ float lane_xor16(float v)

@@ -74,7 +74,9 @@ def test_topk_tie_torture(ops, oracle, n, k):
 
 def test_topk_wide_rows_and_nan(ops, oracle):
     """One wave per row (round 4): rows longer than a wave's first pass (n = 2048: the one-row-per-workgroup form), k > 64
-    (the mask write loops), NaNs (ordered first by torch.topk) and the introselect depth limit (sorted / organ-pipe rows)."""
+    (the mask write loops), NaNs (ordered first by torch.topk) and sorted / organ-pipe / constant rows.  Those rows use 8 to 16 of
+    the 18 partition levels introselect allows at n = 512 (test_select_edges_host.py records it): the depth-limit fallback is
+    reached by the adversary rows of test_gpu_select_edges.py, not here."""
     g = torch.Generator().manual_seed(77)
     x = torch.rand(40, 2048, generator=g)
     x[::3, ::7] = float("nan")

@@ -10,6 +10,15 @@ namespace {
 
 constexpr int kChunk = 16384;           // elements per workgroup
 
+// THE float -> 16-bit conversion of the weight shadows (round to nearest even; F16 = false: bfloat16, true: IEEE half).  The two
+// update kernels and cast_multi_kernel all go through these, so a shadow refreshed from a restored parameter holds the bits the
+// update that produced the parameter wrote.
+template <bool F16> __device__ __forceinline__ uint16_t shadow_bits(float v) { return H16<F16>::from_f32(v); }
+template <bool F16> __device__ __forceinline__ uint2 shadow_bits4(const float4& v)
+{
+    uint2 o; o.x = H16<F16>::pack2(v.x, v.y); o.y = H16<F16>::pack2(v.z, v.w); return o;
+}
+
 // chunk c covers elements [off, off+len) of tensor t;  g' = g + wd*p ; m = mu*m + g' (m starts at 0) ; p -= lr*m
 template <bool F16>
 __global__ __launch_bounds__(256) void sgd_multi_kernel(float* const* __restrict__ p_ptrs, const float* const* __restrict__ g_ptrs,
@@ -47,14 +56,14 @@ __global__ __launch_bounds__(256) void sgd_multi_kernel(float* const* __restrict
             pv.x -= l * mv.x; pv.y -= l * mv.y; pv.z -= l * mv.z; pv.w -= l * mv.w;
             *reinterpret_cast<float4*>(m + i) = mv;
             *reinterpret_cast<float4*>(p + i) = pv;
-            if (h) { uint2 o; o.x = H16<F16>::pack2(pv.x, pv.y); o.y = H16<F16>::pack2(pv.z, pv.w); *reinterpret_cast<uint2*>(h + i) = o; }
+            if (h) *reinterpret_cast<uint2*>(h + i) = shadow_bits4<F16>(pv);
         }
         for (long i = (n & ~3L) + threadIdx.x; i < n; i += 256) {
             bad |= !isfinite(g[i]);
             const float d = g[i] * gsc + w * p[i];
             const float mv = momentum * m[i] + d;
             m[i] = mv; p[i] -= l * mv;
-            if (h) h[i] = H16<F16>::from_f32(p[i]);
+            if (h) h[i] = shadow_bits<F16>(p[i]);
         }
     } else {
         for (long i = threadIdx.x; i < n; i += 256) {
@@ -62,10 +71,44 @@ __global__ __launch_bounds__(256) void sgd_multi_kernel(float* const* __restrict
             const float d = g[i] * gsc + w * p[i];
             const float mv = momentum * m[i] + d;
             m[i] = mv; p[i] -= l * mv;
-            if (h) h[i] = H16<F16>::from_f32(p[i]);
+            if (h) h[i] = shadow_bits<F16>(p[i]);
         }
     }
     if (nonfinite && bad) atomicOr(nonfinite, 1);
+}
+
+// The shadows alone, from the parameters as they are (a restored checkpoint, a roll-back): h[t] = 16-bit(p[t]) over the same chunk
+// tables; h_ptrs[t] == NULL skips tensor t.  Streaming: 16-byte loads / 8-byte stores where the chunk's addresses allow, four in
+// flight per thread, and a scalar tail.
+template <bool F16>
+__global__ __launch_bounds__(256) void cast_multi_kernel(const float* const* __restrict__ p_ptrs, uint16_t* const* __restrict__ h_ptrs,
+    const int* __restrict__ chunk_tensor, const long* __restrict__ chunk_off, const long* __restrict__ numel)
+{
+    const int t = chunk_tensor[blockIdx.x];
+    if (!h_ptrs[t]) return;
+    const long off = chunk_off[blockIdx.x];
+    const long n = min((long)kChunk, numel[t] - off);
+    const float* __restrict__ p = p_ptrs[t] + off;
+    uint16_t* __restrict__ h = h_ptrs[t] + off;
+    long done = 0;
+    if ((reinterpret_cast<uintptr_t>(p) & 15) == 0 && (reinterpret_cast<uintptr_t>(h) & 7) == 0) {
+        const long n4 = n >> 2;
+        for (long i0 = threadIdx.x; i0 < n4; i0 += 256 * 4) {
+            float4 v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long i = i0 + j * 256;
+                if (i < n4) v[j] = *reinterpret_cast<const float4*>(p + i * 4);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long i = i0 + j * 256;
+                if (i < n4) *reinterpret_cast<uint2*>(h + i * 4) = shadow_bits4<F16>(v[j]);
+            }
+        }
+        done = n & ~3L;
+    }
+    for (long i = done + threadIdx.x; i < n; i += 256) h[i] = shadow_bits<F16>(p[i]);
 }
 
 // found[0] |= 1 when any gradient element of the step is inf / nan (torch._amp_foreach_non_finite_check_and_unscale_'s
@@ -266,7 +309,7 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(float* const* __restri
         const float denom = sqrtf(vv) / bc2s + eps;
         pv -= step_size * (mv / denom);
         m[i] = mv; v[i] = vv; p[i] = pv;
-        if (h) h[i] = H16<F16>::from_f32(pv);
+        if (h) h[i] = shadow_bits<F16>(pv);
     }
     if (nonfinite && __builtin_amdgcn_ballot_w64(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(nonfinite, 1);
 }
@@ -331,6 +374,22 @@ extern "C" int editor_sgd_multi(float* const* p_ptrs, const float* const* g_ptrs
     else
         hipLaunchKernelGGL(sgd_multi_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, stream, p_ptrs, g_ptrs, m_ptrs,
                            chunk_tensor, chunk_off, numel, lr, wd, momentum, h_ptrs, nonfinite, inv_scale, skip);
+    EDITOR_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int editor_cast_multi(const float* const* p_ptrs, uint16_t* const* h_ptrs, const int* chunk_tensor, const long* chunk_off,
+    const long* numel, long nchunks, int shadow_dtype, hipStream_t stream)
+{
+    if (!p_ptrs || !h_ptrs || !chunk_tensor || !chunk_off || !numel || nchunks < 0 || (shadow_dtype != 1 && shadow_dtype != 2))
+        return (int)hipErrorInvalidValue;
+    if (nchunks < 1) return 0;
+    if (shadow_dtype == 2)
+        hipLaunchKernelGGL(cast_multi_kernel<true>, dim3((unsigned)nchunks), dim3(256), 0, stream, p_ptrs, h_ptrs, chunk_tensor,
+                           chunk_off, numel);
+    else
+        hipLaunchKernelGGL(cast_multi_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, stream, p_ptrs, h_ptrs, chunk_tensor,
+                           chunk_off, numel);
     EDITOR_LAUNCH_CHECK();
     return 0;
 }

@@ -18,8 +18,11 @@ per-iteration `add_scalar('Loss', loss.item(), epoch)` is a host read; what is w
 autocast and no torch GradScaler (the model does its own typing); `do_train` returns `best_index`; `do_inference` computes and
 logs the metrics and returns `(cmc, mAP)` (the reference's stops after the feature loop).  The module imports without a GPU and
 without the built library, which is loaded by the first launch; there is no fallback to torch for the meters."""
+import contextlib
 import logging
 import os
+import random
+import re
 import time
 import warnings
 
@@ -92,6 +95,64 @@ class DeviceMeters:
         return {"loss_avg": loss_sum / samples if samples else 0.0, "acc_avg": acc_sum / steps if steps else 0.0,
                 "loss_sum": loss_sum, "samples": samples, "acc_sum": acc_sum, "steps": steps,
                 "last_correct": int(last[0]), "last_batch": int(last[1])}
+
+
+def _map_tensors(obj, fn):
+    if isinstance(obj, torch.Tensor):
+        return fn(obj)
+    if isinstance(obj, dict):
+        return {k: _map_tensors(v, fn) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_map_tensors(v, fn) for v in obj)
+    return obj
+
+
+def _flatten(obj, prefix=""):
+    """Nested dicts (and lists of dicts: param_groups) -> {dotted key: leaf}."""
+    if isinstance(obj, dict):
+        items = obj.items()
+    elif isinstance(obj, (list, tuple)) and obj and all(isinstance(v, dict) for v in obj):
+        items = enumerate(obj)
+    else:
+        return {prefix[:-1]: obj}
+    flat = {}
+    for k, v in items:
+        flat.update(_flatten(v, "%s%s." % (prefix, k)))
+    return flat
+
+
+def _first_difference(mine, theirs, prefix):
+    """(key, what) of the first key that `theirs` lacks, has in excess or holds as a tensor of another shape; None if none."""
+    for k, v in mine.items():
+        if k not in theirs:
+            return prefix + str(k), "missing"
+        t = theirs[k]
+        if isinstance(v, torch.Tensor) != isinstance(t, torch.Tensor):
+            return prefix + str(k), "a tensor on one side only"
+        if isinstance(v, torch.Tensor) and tuple(v.shape) != tuple(t.shape):
+            return prefix + str(k), "shape %s here, %s in the state" % (tuple(v.shape), tuple(t.shape))
+    for k in theirs:
+        if k not in mine:
+            return prefix + str(k), "unexpected"
+    return None
+
+
+def _plain(v):
+    return tuple(float(x) for x in v) if isinstance(v, (list, tuple)) else float(v)
+
+
+def _dtype_name(dtype):
+    return None if dtype is None else str(dtype).replace("torch.", "")
+
+
+def _compute_dtype(model):
+    """cfg.MODEL.COMPUTE_DTYPE as the model took it: 'bf16' | 'f16' | 'f16x2' | 'f32' (None: not an EDITOR model)."""
+    act = getattr(model, "act_dtype", None)
+    if act is None:
+        return None
+    if getattr(model, "split_fwd", False):
+        return "f16x2"
+    return {torch.bfloat16: "bf16", torch.float16: "f16", torch.float32: "f32"}[act]
 
 
 def _signature(img, *ids):
@@ -203,6 +264,94 @@ class TrainStep:
         self._graph.replay()                                              # (the capture recorded the step; this runs it)
         return self._static_loss
 
+    # -- the whole state of the iteration: snapshot, roll-back, resume ---------------------------------------------------------
+    def state_dict(self, device=False):
+        """Everything the next step reads: the model's state dict and drop-path counter, optimizer (momentum / Adam moments and
+        step count, param_groups), scaler, meters, and the count of eager warm-up steps.  device=True: the tensors are device
+        clones (a snapshot to roll back to, one clone of every parameter, buffer and momentum tensor); else CPU copies (what
+        save_checkpoint writes).  Synchronises (the scalar states are read); call it between steps."""
+        keep = (lambda t: t.detach().clone()) if device else (lambda t: t.detach().cpu() if t.is_cuda else t.detach().clone())
+        return {"model": {k: keep(v) for k, v in self.model.state_dict().items()},
+                "model_rng": self.model.rng_state() if hasattr(self.model, "rng_state") else None,
+                "optimizer": _map_tensors(self.optimizer.state_dict(), keep),
+                "optimizer_class": type(self.optimizer).__name__,
+                "scaler": None if self.scaler is None else self.scaler.state_dict(),
+                "meters": None if self.meters is None else keep(self.meters._buf),
+                "eager_steps": self._eager_steps,
+                "compute_dtype": _compute_dtype(self.model), "shadow_dtype": _dtype_name(getattr(self.optimizer, "shadow_dtype", None))}
+
+    def _mismatch(self, sd):
+        """The first key of `sd` that does not fit this step, or None.  Reads shapes only."""
+        want = ("model", "model_rng", "optimizer", "optimizer_class", "scaler", "meters", "eager_steps", "compute_dtype", "shadow_dtype")
+        for k in want:
+            if k not in sd:
+                return k, "missing"
+        for k in sd:
+            if k not in want:
+                return k, "unexpected"
+        if sd["compute_dtype"] != _compute_dtype(self.model):
+            return "compute_dtype", "%s here, %s in the state" % (_compute_dtype(self.model), sd["compute_dtype"])
+        mine = _dtype_name(getattr(self.optimizer, "shadow_dtype", None))
+        if sd["shadow_dtype"] != mine:
+            return "shadow_dtype", "%s here, %s in the state" % (mine, sd["shadow_dtype"])
+        if sd["optimizer_class"] != type(self.optimizer).__name__:
+            return "optimizer_class", "%s here, %s in the state" % (type(self.optimizer).__name__, sd["optimizer_class"])
+        for k, here in (("scaler", self.scaler), ("meters", self.meters)):
+            if (sd[k] is None) != (here is None):
+                return k, "present on one side only"
+        bad = _first_difference(self.model.state_dict(), sd["model"], "model.")
+        if bad is None:
+            bad = _first_difference(_flatten(self.optimizer.state_dict()), _flatten(sd["optimizer"]), "optimizer.")
+        if bad is None and self.meters is not None:
+            bad = _first_difference({"meters": self.meters._buf}, {"meters": sd["meters"]}, "")
+        if bad is None and self.captured:
+            # what a launch takes BY VALUE is part of the captured graph: a state that changes it needs a new TrainStep
+            for k in ("betas", "eps"):
+                got = {_plain(g[k]) for g in sd["optimizer"]["param_groups"] if k in g}
+                if got and got != {_plain(getattr(self.optimizer, k))}:
+                    return "optimizer.param_groups." + k, "differs from the value the captured graph was recorded with"
+            for k in ("growth_factor", "backoff_factor", "growth_interval") if self.scaler is not None else ():
+                if float(sd["scaler"][k]) != float(getattr(self.scaler, k)):
+                    return "scaler." + k, "differs from the value the captured graph was recorded with"
+        return bad
+
+    def load_state_dict(self, sd):
+        """Restore what state_dict() returned IN PLACE, on the step's own stream: copy_ into the existing parameters, buffers,
+        momentum tensors and the meters' buffer, set_rng_state into the existing counter, then optimizer.refresh_operands() -
+        without it every 16-bit shadow, W^T copy and hi / lo pair would still hold the weights from before.  Nothing is
+        re-allocated, so a captured graph stays valid (`captured` does not change) and its next replay continues from the
+        restored state.  Warm-up belongs to this object and its process: `eager_steps` of the state is not taken over, a fresh
+        graph=True step still runs its own warm-up before it captures.
+
+        ValueError - naming the first offending key, before anything is written - on a missing or extra key, another shape,
+        another optimizer class, another COMPUTE_DTYPE / shadow dtype, or a scaler (meters) present on one side only."""
+        bad = self._mismatch(sd)
+        if bad is not None:
+            raise ValueError("TrainStep.load_state_dict: '%s': %s" % bad)
+        dev = _model_device(self.model)
+        if dev is None or dev.type != "cuda":
+            return self._restore(sd)
+        if self._stream is None:
+            self._stream = torch.cuda.Stream(device=dev)
+        cur = torch.cuda.current_stream(dev)
+        self._stream.wait_stream(cur)
+        with torch.cuda.stream(self._stream):
+            self._restore(sd)
+        cur.wait_stream(self._stream)
+
+    @torch.no_grad()
+    def _restore(self, sd):
+        for k, v in self.model.state_dict().items():
+            v.copy_(sd["model"][k])
+        if hasattr(self.model, "set_rng_state"):
+            self.model.set_rng_state(sd["model_rng"])
+        self.optimizer.load_state_dict(sd["optimizer"])
+        if self.scaler is not None:
+            self.scaler.load_state_dict(sd["scaler"])
+        if self.meters is not None:
+            self.meters._buf.copy_(sd["meters"])
+        self.optimizer.refresh_operands()
+
     def _copy_in(self, img, target, cam, view):
         s_img, s_ids = self._static
         for k, v in img.items():
@@ -237,6 +386,91 @@ def _is_main(cfg):
 
 def _save(model, path):
     torch.save(model.state_dict(), path)
+
+
+# ---- full-state checkpoints ------------------------------------------------------------------------------------------------------
+
+CHECKPOINT_FORMAT = 1
+_STATE_FILE = re.compile(r"_state_(\d+)\.pth$")
+
+
+def _atomic_save(obj, path):
+    """torch.save under a temporary name in the same directory, then os.replace: a reader (and a run killed half-way) sees the
+    old file or the new one, never a part of either."""
+    tmp = "%s.tmp.%d" % (path, os.getpid())
+    try:
+        torch.save(obj, tmp)
+        os.replace(tmp, path)
+    except BaseException:
+        with contextlib.suppress(OSError):
+            os.remove(tmp)
+        raise
+
+
+def save_checkpoint(path, step, *, epoch, scheduler=None, loaders=(), best_index=None, extra=None):
+    """Everything a restarted process needs to continue as if it had not stopped, as ONE torch.save of a plain dict with CPU tensors:
+
+        format         1
+        epoch          the epoch just finished (a resumed do_train continues at epoch + 1)
+        step           step.state_dict(): model, drop-path counter, optimizer, scaler, meters (TrainStep.state_dict)
+        scheduler      scheduler.state_dict() or None
+        loader_epochs  [loader.epoch or None]: the loaders' batches are a function of (seed, epoch); a loader without an `epoch`
+                       attribute is skipped (None)
+        best_index     {'mAP', 'Rank-1', 'Rank-5', 'Rank-10'} as floats, or None
+        rng            {'python': random.getstate(), 'numpy': numpy.random.get_state(), 'torch': torch.get_rng_state()} - the global
+                       generators the identity samplers draw from and torch's CPU generator.  Nothing in the step or the loaders
+                       draws from torch's device generator (the drop-path counter is the model's own state).
+        compute_dtype  cfg.MODEL.COMPUTE_DTYPE of the model
+        extra          the caller's own entry, if given
+
+    Synchronises the device (the state is copied to the host) and writes atomically."""
+    import numpy as np
+    sd = step.state_dict()
+    ckpt = {"format": CHECKPOINT_FORMAT, "epoch": int(epoch), "step": sd,
+            "scheduler": None if scheduler is None else scheduler.state_dict(),
+            "loader_epochs": [int(ld.epoch) if hasattr(ld, "epoch") else None for ld in loaders],
+            "best_index": None if best_index is None else {k: float(v) for k, v in best_index.items()},
+            "rng": {"python": random.getstate(), "numpy": np.random.get_state(), "torch": torch.get_rng_state()},
+            "compute_dtype": sd.get("compute_dtype")}
+    if extra is not None:
+        ckpt["extra"] = extra
+    _atomic_save(ckpt, path)
+
+
+def load_checkpoint(path, step, *, scheduler=None, loaders=()):
+    """Restore what save_checkpoint wrote - step.load_state_dict (which refuses a state that does not fit, before anything is
+    written), the scheduler, the loaders' epoch numbers and the three host generators - and return the file's dict (its `epoch`,
+    `best_index` and `extra` are the caller's to use).  ValueError for a file of another format."""
+    import numpy as np
+    ckpt = torch.load(path, map_location="cpu", weights_only=False)
+    if not isinstance(ckpt, dict) or ckpt.get("format") != CHECKPOINT_FORMAT:
+        raise ValueError("load_checkpoint: %s is not a format-%d state file (format: %r)"
+                         % (path, CHECKPOINT_FORMAT, ckpt.get("format") if isinstance(ckpt, dict) else type(ckpt).__name__))
+    missing = [k for k in ("epoch", "step", "scheduler", "loader_epochs", "best_index", "rng", "compute_dtype") if k not in ckpt]
+    if missing:
+        raise ValueError("load_checkpoint: %s lacks '%s'" % (path, missing[0]))
+    step.load_state_dict(ckpt["step"])
+    if scheduler is not None and ckpt["scheduler"] is not None:
+        scheduler.load_state_dict(ckpt["scheduler"])
+    for ld, ep in zip(loaders, ckpt["loader_epochs"]):
+        if ep is not None and hasattr(ld, "epoch"):
+            ld.epoch = int(ep)
+    rng = ckpt["rng"]
+    random.setstate(rng["python"])
+    np.random.set_state(rng["numpy"])
+    torch.set_rng_state(rng["torch"])
+    return ckpt
+
+
+def latest_state_file(out_dir, name):
+    """<out_dir>/<name>_state_<epoch>.pth with the highest epoch, or None (what resume='auto' loads)."""
+    best = None
+    if os.path.isdir(out_dir):
+        for fn in os.listdir(out_dir):
+            m = _STATE_FILE.search(fn)
+            if m and fn == "%s_state_%s.pth" % (name, m.group(1)) and (best is None or int(m.group(1)) > best[0]):
+                best = (int(m.group(1)), os.path.join(out_dir, fn))
+    return None if best is None else best[1]
 
 
 def _model_device(model):
@@ -285,14 +519,21 @@ def _rank(cmc, r):
 
 
 def do_train(cfg, model, center_criterion, train_loader, val_loader, optimizer, optimizer_center, scheduler, loss_fn, num_query,
-             local_rank, *, writer=None, scaler=None, graph=False, logger=None):
+             local_rank, *, writer=None, scaler=None, graph=False, logger=None, save_state=False, resume=None):
     """engine/processor.py:23-214 with its positional signature (train_net.py:78-89 calls it unchanged).  writer: anything with
     `add_scalar` (None: nothing is written; tensorboard is never imported here); scaler: a DeviceGradScaler; graph: capture the
     step into a hipGraph (TrainStep).  Per epoch: meters and evaluator reset, scheduler.step(epoch), model.train(), one
     TrainStep.step per batch, a log line (one meters.read()) every SOLVER.LOG_PERIOD iterations, one device synchronisation and
     the `Epoch .. done` line, a checkpoint every CHECKPOINT_PERIOD, an evaluation every EVAL_PERIOD.  Returns best_index.
     center_criterion, optimizer_center and local_rank are taken for the signature's sake: the reference's loop only zeroes the
-    centre optimizer's (never computed) gradients, and the model is expected on its device already."""
+    centre optimizer's (never computed) gradients, and the model is expected on its device already.
+
+    save_state=True: every CHECKPOINT_PERIOD epoch ALSO writes <OUTPUT_DIR>/<NAME>_state_<epoch>.pth (save_checkpoint: the whole
+    training state), after that epoch's evaluation so that best_index is current; the previous state file is removed once the new
+    one is in place.  resume=<path> loads such a file before the first epoch and continues at its epoch + 1 exactly as the
+    uninterrupted run would have (same batches, same drop-path draws, same meters / scheduler / evaluator handling);
+    resume='auto' takes the highest-numbered state file of OUTPUT_DIR and starts afresh if there is none.  With MODEL.DIST_TRAIN
+    only the main rank writes and every rank loads the same file (checked on one rank only: no multi-rank run exists here)."""
     log_period, checkpoint_period, eval_period = cfg.SOLVER.LOG_PERIOD, cfg.SOLVER.CHECKPOINT_PERIOD, cfg.SOLVER.EVAL_PERIOD
     logger = logger or logging.getLogger("EDITOR.train")
     logger.info("start training")
@@ -311,7 +552,18 @@ def do_train(cfg, model, center_criterion, train_loader, val_loader, optimizer, 
     name = os.path.join(cfg.OUTPUT_DIR, cfg.MODEL.NAME)
 
     best_index = {"mAP": 0, "Rank-1": 0, "Rank-5": 0, "Rank-10": 0}
-    for epoch in range(1, cfg.SOLVER.MAX_EPOCHS + 1):
+    first_epoch, state_file = 1, None
+    if resume is not None:
+        path = latest_state_file(cfg.OUTPUT_DIR, cfg.MODEL.NAME) if resume == "auto" else resume
+        if path is not None:
+            ckpt = load_checkpoint(path, step, scheduler=scheduler, loaders=(train_loader, val_loader))
+            first_epoch = ckpt["epoch"] + 1
+            if ckpt["best_index"] is not None:
+                best_index.update(ckpt["best_index"])
+            if os.path.dirname(os.path.abspath(path)) == os.path.abspath(cfg.OUTPUT_DIR) and _STATE_FILE.search(path):
+                state_file = path                                          # ours: replaced by the next one this run writes
+            logger.info("resumed from {} (epoch {})".format(path, ckpt["epoch"]))
+    for epoch in range(first_epoch, cfg.SOLVER.MAX_EPOCHS + 1):
         start_time = time.time()
         meters.reset()
         evaluator.reset()
@@ -351,6 +603,15 @@ def do_train(cfg, model, center_criterion, train_loader, val_loader, optimizer, 
                 logger.info("Best Multi-Modal {}: {:.2%}".format(key, best_index[key]))
             if dev is not None and dev.type == "cuda":
                 torch.cuda.empty_cache()
+
+        if save_state and epoch % checkpoint_period == 0 and main:
+            os.makedirs(cfg.OUTPUT_DIR, exist_ok=True)
+            new = name + "_state_{}.pth".format(epoch)
+            save_checkpoint(new, step, epoch=epoch, scheduler=scheduler, loaders=(train_loader, val_loader), best_index=best_index)
+            if state_file is not None and os.path.abspath(state_file) != os.path.abspath(new):
+                with contextlib.suppress(OSError):
+                    os.remove(state_file)
+            state_file = new
     return best_index
 
 

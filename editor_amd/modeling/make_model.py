@@ -370,6 +370,22 @@ class EDITOR(nn.Module):
             sd[k.replace("module.", "")].copy_(param_dict[k])
         print("Loading pretrained model from {}".format(trained_path))
 
+    # -- the drop-path generator (a device counter, neither parameter nor buffer nor state-dict key) ------------------
+    def rng_state(self):
+        """The drop-path counter as a Python int (one device read); None before the first training forward seeded it."""
+        return None if self._drop_state is None else int(self._drop_state.item())
+
+    def set_rng_state(self, v):
+        """Continue the drop-path draws from counter `v` (what rng_state() returned): written in place into the existing counter -
+        a captured step reads that address - or, before the first training forward, created with this value on the parameters'
+        device, so that the lazy seeding from torch.initial_seed() does not replace it.  None: nothing to restore."""
+        if v is None:
+            return
+        if self._drop_state is not None:
+            self._drop_state.fill_(int(v))
+        else:
+            self._drop_state = torch.full((1,), int(v), dtype=torch.int64, device=next(self.parameters()).device)
+
     # -- data-parallel gradient buckets (editor_amd.ddp.GradBuckets) ------------------------------------------------
     def grad_segments(self):
         """Transformer blocks in the order their gradients become READY in the backward: joint HMA block, the per-modality

@@ -191,7 +191,41 @@ class FusedSGD:
                 b.copy_(st["momentum_buffer"])
             else:
                 b.zero_()
+        self._found.zero_()                  # the flags speak of steps the restored state never took
+        self._nonfinite.zero_()
         self.sync_param_groups()
+
+    @torch.no_grad()
+    def refresh_operands(self):
+        """Rebuild every operand copy from the parameters AS THEY ARE - after a checkpoint or a snapshot was written into them in
+        place (`p.copy_`): the 16-bit shadows (editor_cast_multi: the bits the update kernel writes), the k-major W^T copies
+        (editor_transpose_multi) and, with split_pairs, the hi / lo pairs (editor_split_multi), all at their existing addresses -
+        a captured hipGraph that reads them stays valid - and installed in the operand cache of editor_amd.functional for EVERY
+        weight that has them (a weight that never had a gradient has a shadow too, and the update kernel never wrote it).  Three
+        launches on the current stream, no host read.  Not while a stream is capturing: a refresh baked into a graph would run at
+        every replay."""
+        from . import functional
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedSGD.refresh_operands: the current stream is capturing; refresh between replays")
+        with torch.cuda.device(self.device):
+            if self.shadow_dtype is not None:
+                _lib.call("editor_cast_multi", self.p_ptrs, self.h_ptrs, self.chunk_t, self.chunk_o, self.numel, self.nchunks,
+                          2 if self.shadow_dtype == torch.float16 else 1)
+                if self._tr is not None:
+                    tr = self._tr
+                    _lib.call("editor_transpose_multi", tr["src"], tr["dst"], tr["rows"], tr["cols"], tr["tile_t"], tr["tile_r"],
+                              tr["tile_c"], tr["n"])
+            if self.pairs is not None:
+                from . import ops
+                _lib.call("editor_split_multi", self.p_ptrs, self.hi_ptrs, self.lo_ptrs, self.chunk_t, self.chunk_o, self.numel,
+                          self.nchunks, float(ops.SPLIT_WSCALE))
+        functional.invalidate_weight_cache()
+        if self.shadow_dtype is not None:
+            functional.install_weight_copies((p, h) for (_, p), h in zip(self.params, self.shadows) if h is not None)
+            functional.install_weight_copies(((p, h) for (_, p), h in zip(self.params, self.shadows_t) if h is not None),
+                                             transposed=True)
+        if self.pairs is not None:
+            functional.install_weight_pairs((p, pr[0], pr[1]) for (_, p), pr in zip(self.params, self.pairs) if pr is not None)
 
     @torch.no_grad()
     def step(self):
@@ -303,7 +337,18 @@ class FusedAdamW(FusedSGD):
 
     def load_state_dict(self, sd):
         state = sd["state"]
+        # the kernel is launched with ONE (betas, eps): the loaded groups' values become it; groups that disagree are refused
+        # before anything is written
+        hyper = {(tuple(float(b) for b in g.get("betas", self.betas)), float(g.get("eps", self.eps))) for g in sd["param_groups"]}
+        if len(hyper) > 1:
+            raise ValueError("FusedAdamW.load_state_dict: per-group betas / eps differ (%s); the update kernel takes one pair"
+                             % sorted(hyper)[:2])
         super().load_state_dict({"state": {}, "param_groups": sd["param_groups"]})
+        if hyper:
+            (self.betas, self.eps), = hyper
+            self.defaults.update(betas=self.betas, eps=self.eps)
+            for g in self.param_groups:
+                g.update(betas=self.betas, eps=self.eps)
         t = 0.0
         for i, (m, v) in enumerate(zip(self.bufs, self.bufs_sq)):
             st = state.get(i, state.get(str(i)))
@@ -368,5 +413,6 @@ class DeviceGradScaler:
         self._scale.fill_(float(sd["scale"]))
         self._inv_scale.fill_(1.0 / float(sd["scale"]))
         self._tracker.fill_(int(sd.get("_growth_tracker", 0)))
+        self._found.zero_()
         self.growth_factor, self.backoff_factor = float(sd["growth_factor"]), float(sd["backoff_factor"])
         self.growth_interval = int(sd["growth_interval"])

@@ -654,6 +654,12 @@ int editor_adamw_multi(float* const* p_ptrs, const float* const* g_ptrs, float* 
                        const int* chunk_tensor, const long* chunk_off, const long* numel, const float* lr, const float* wd,
                        double beta1, double beta2, float eps, float* step, long nchunks, uint16_t* const* h_ptrs, int shadow_dtype,
                        int* nonfinite, const float* inv_scale, const int* skip, editor_stream_t stream);
+/* The 16-bit shadows alone, from the parameters as they are: h_ptrs[t] = 16-bit(p_ptrs[t]) over the chunk tables of
+ * editor_sgd_multi, in ONE launch, with the bits the update kernels write (round to nearest even); h_ptrs[t] == NULL skips
+ * tensor t; shadow_dtype: 1 = bf16, 2 = f16.  For a checkpoint restored into the parameters in place (FusedSGD.refresh_operands):
+ * follow it with editor_transpose_multi / editor_split_multi.  NULL tables, nchunks < 0 or another dtype: hipErrorInvalidValue. */
+int editor_cast_multi(const float* const* p_ptrs, uint16_t* const* h_ptrs, const int* chunk_tensor, const long* chunk_off,
+                      const long* numel, long nchunks, int shadow_dtype, editor_stream_t stream);
 /* amp.GradScaler's overflow check (engine/processor.py:94-96 -> torch/amp/grad_scaler.py): found[0] |= 1 (and sticky[0] |= 1,
  * optional) when any gradient element of the tensors in the chunk tables is inf / nan.  Run BEFORE editor_sgd_multi with
  * skip = found. */
